@@ -13,9 +13,16 @@ lookup of its tables + the RCCL all-gather of the slabs + the concat assembly, s
 the whole-job throughput is B*T*P lookups per step time ("scaling": "strong").
 
 Prints ONE JSON line on rank 0 with the roofline of the dominant kernel
-(k_pooled_vec, HIP events on the launch stream) and the CPU baseline (the oracle's
-multithreaded restatement of the reference CPU path, timed on this host's cores on
-the same tables and indices, with its output compared bit-for-bit to the GPU's).
+(k_pooled_vec, HIP events on the launch stream around the timed steps).
+
+A plain run sets up, warms up, times --steps steps, writes the outputs of the last
+timed step if --dump-outputs DIR is given, and prints the line.  --full adds every
+other measurement: the CPU baseline (the oracle's multithreaded restatement of the
+reference CPU path, timed on this host's cores on the same tables and indices, with
+its output compared bit-for-bit to the GPU's), the table classes of the headline
+launch, configs 2 and 4, config 3 at prependrows 16 and with Float16 tables, and for
+the sharded step the lookup-only time (with the roofline derived from it), the
+all-to-all layout and --p2p.
 """
 from __future__ import annotations
 
@@ -36,6 +43,7 @@ DIM, POOL, BATCH = 128, 20, 65536
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md, chip-level parameters)
 HBM_COPY_GBS = 6290.0  # measured float4-copy ceiling (MI355X_MICROARCH.md:36), SURVEY.md §8d
 TABLE_SEED, INDEX_SEED = 1000, 2000
+DUMP_BYTES, DUMP_SEED = 48 << 20, 5000  # --dump-outputs: size cap and row-sample seed
 
 
 INFINITY_CACHE = 256 << 20  # MI355X die-level L3 (MI355X_MICROARCH.md, Infinity Cache)
@@ -85,13 +93,22 @@ def parse():
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--batch", type=int, default=BATCH)
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline figure: CPU baseline and bit "
+                        "comparison, table classes, configs 2 and 4, config 3 at k = 16 and in "
+                        "Float16, the sharded step's lookup-only time, all-to-all and --p2p")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed as "
+                        "DIR/<name>.npy (float32; a fixed seeded sample of the rows above "
+                        f"{DUMP_BYTES >> 20} MiB)")
     p.add_argument("--cpu-seconds", type=float, default=10.0,
-                   help="target CPU-baseline sample duration (0 disables)")
+                   help="--full: target CPU-baseline sample duration (0 disables)")
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="CPU-baseline threads; 0 = every host core (os.cpu_count())")
     p.add_argument("--no-check", action="store_true", help="skip the CPU/GPU bit comparison")
     p.add_argument("--no-extra", action="store_true",
-                   help="skip the config-2 (gather) and config-4 (Zipf + SGD) measurements")
+                   help="--full: skip the table classes and the config-2 (gather), config-3 "
+                        "variants and config-4 (Zipf + SGD) measurements")
     p.add_argument("--force-shard", action="store_true",
                    help="use the sharded (all-gather + concat) step even on one rank")
     p.add_argument("--plan", choices=["featurewise", "tablewise"], default="tablewise",
@@ -103,9 +120,11 @@ def parse():
                    help="N > 1 process group: nccl (= RCCL on ROCm) or gloo (rehearsal of "
                         "the N > 1 path with several ranks sharing one GPU)")
     p.add_argument("--p2p", action="store_true",
-                   help="N>1: also time the one-sided exchange (IPC-mapped peers, et_push_cols)")
+                   help="--full, N > 1: also time the one-sided exchange (IPC-mapped peers, "
+                        "et_push_cols)")
     p.add_argument("--no-alltoall", action="store_true",
-                   help="N > 1: skip the extra all-to-all (batch-sliced output) measurement")
+                   help="--full, N > 1: skip the extra all-to-all (batch-sliced output) "
+                        "measurement")
     p.add_argument("--subset", choices=["all", "heavy", "light"], default="all",
                    help="calibration only: tables above / below 4 MiB")
     p.add_argument("--rows", type=int, default=0,
@@ -114,7 +133,32 @@ def parse():
                    help="calibration only: drop the tables with fewer rows")
     p.add_argument("--max-rows", type=int, default=0,
                    help="calibration only: drop the tables with more rows (0 = no limit)")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(dirpath, dst):
+    """Write the destination of the last timed step — what a caller of maplookup_ (or
+    of the sharded step) receives — as DIR/maplookup_dst.npy.  A destination larger than
+    DUMP_BYTES is cut to a sorted sample of its rows (bags) drawn without replacement
+    from a fixed seed, so two runs with the same arguments write the same rows."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirpath, exist_ok=True)
+    torch.cuda.synchronize()
+    B, ld = dst.shape
+    keep = max(1, DUMP_BYTES // (ld * 4))
+    info = {"shape": [B, ld], "rows_written": B, "sample_seed": None}
+    if B > keep:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, size=keep, replace=False))
+        dst = dst[torch.from_numpy(rows).to(dst.device)]
+        info.update(rows_written=keep, sample_seed=DUMP_SEED)
+    np.save(os.path.join(dirpath, "maplookup_dst.npy"),
+            dst.to(torch.float32).cpu().numpy())
+    return {"maplookup_dst": info}
 
 
 def make_tables(et, L, tids, device):
@@ -666,7 +710,11 @@ def main():
                          device=device if args.backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    if sharded:  # lookup-only time: the chunked lookups alone, same launches, no exchange
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, dst)
+    extra = args.full and not args.no_extra
+    if sharded and args.full:  # lookup-only time: the chunked lookups alone, no exchange
         torch.cuda.synchronize()
         for k in range(args.steps):
             ev[k][0].record(stream)
@@ -757,11 +805,17 @@ def main():
             "kernel_ms_median": kernel_ms_median,
         },
     }
-    if not sharded and world == 1 and not args.no_extra:
+    if dumped:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, **dumped}
+    if sharded and not args.full:
+        # the roofline of the sharded step is that of its lookup-only time (--full)
+        del result["roofline"]
+    if not sharded and world == 1 and extra:
         result["roofline"]["classes"] = table_classes(et, tables, idx, mine, B, stream,
                                                       kernel_ms)
     if sharded:
-        result["lookup_only_ms"] = kernel_ms
+        if args.full:
+            result["lookup_only_ms"] = kernel_ms
         result["slab_cols"] = plan.slab_ld
         # what every rank holds: its tables (or feature slices) only
         mem = {"rank": rank, "tables": mine, "pieces": [(p.table, p.f0, p.dim) for p in pieces],
@@ -772,19 +826,19 @@ def main():
         else:
             every = [mem]
         result["per_rank"] = every
-        if world > 1 and not args.no_alltoall:
+        if world > 1 and args.full and not args.no_alltoall:
             try:  # an extra measurement: never lose the main line to it
                 result["alltoall"] = bench_alltoall(plan, rank, world, B, device, tables, idx,
                                                     max(5, args.steps // 2), 2)
             except Exception as e:  # noqa: BLE001
                 result["alltoall"] = {"error": f"{type(e).__name__}: {e}"}
-        if world > 1 and args.p2p:
+        if world > 1 and args.full and args.p2p:
             try:
                 result["p2p"] = bench_p2p(plan, rank, world, B, device, tables, idx,
                                           max(5, args.steps // 2), 2, args.chunks)
             except Exception as e:  # noqa: BLE001
                 result["p2p"] = {"error": f"{type(e).__name__}: {e}"}
-    if world == 1 and not args.no_extra and not sharded:
+    if world == 1 and extra and not sharded:
         # config 3 also at prependrows k = 16 (dst ld = 16 + 3328)
         dst16 = torch.empty((B, 16 + sum(dims)), dtype=torch.float32, device=device)
         ms16 = _timed(lambda: et.maplookup_(et.PreallocationStrategy(16), dst16, tables, idx),
@@ -792,14 +846,14 @@ def main():
         result["config3_prepend16"] = {"kernel_ms": ms16,
                                        "lookups_per_s": lookups_per_step / (ms16 * 1e-3)}
         del dst16
-    if world == 1 and not args.no_extra:
+    if world == 1 and extra:
         result["config3_fp16"] = bench_config3_fp16(et, L, mine, idx, device, 20, 3, B)
         # config 2 (which captures a HIP graph) before config 4: since round 5 the library
         # opens the exact update's side queues at its first call, so queues opened later (a
         # capture's, another stream's) no longer land on the caller's pipe
         result["config2_gather"] = bench_config2(et, L, device, 320, 2)
         result["config4_zipf_update"] = bench_config4(et, tables, mine, device, 10, 2, B)
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if rank == 0 and world == 1 and args.full and args.cpu_seconds > 0:
         gpu_out = None if args.no_check else dst.cpu().numpy()
         if args.cpu_threads:
             result["cpu_baseline"] = cpu_baseline(gpu_out, idx, B, args.cpu_seconds,

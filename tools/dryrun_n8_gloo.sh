@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p "$OUT"
 for plan in tablewise featurewise; do
   timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
-    --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 8 --backend gloo --plan $plan \
+    --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 8 --full --backend gloo --plan $plan \
     --batch 4096 --steps 2 --warmup 1 --no-alltoall > "$OUT/$plan.json" 2> "$OUT/$plan.err" \
     || { echo DRYRUN_FAIL $plan; tail -20 "$OUT/$plan.err"; exit 1; }
   echo "$plan ok"

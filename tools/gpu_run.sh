@@ -6,9 +6,9 @@
 #   tests            pytest -m gpu (all GPU tests)
 #   tests:EXPR       pytest -m gpu -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   bench            python bench.py (the driver's default run) -> bench.json
-#   trace            rocprofv3 --kernel-trace --stats of bench.py --steps 20 --warmup 3
-#   tracehead        the same with --no-extra (only the headline launches)
+#   bench            python bench.py --full (every measurement) -> bench.json
+#   trace            rocprofv3 --kernel-trace --stats of bench.py --full --steps 20 --warmup 3
+#   tracehead        the same without --full (only the headline launches)
 #   pmc              PMC traffic of the headline kernel (tools/pmc_traffic.sh, tools/traffic.py)
 #   exact            kernel trace of one exact config-4 update + its timeline
 #   cfg2             config 2: kernel trace (graph and eager: duration vs gap) + PMC traffic
@@ -56,14 +56,14 @@ for step in "$@"; do
         || die smoke "$OUT/smoke.log"
       tail -1 "$OUT/smoke.log" ;;
     bench)
-      timeout -k 10 500 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || die bench "$OUT/bench.err"
+      timeout -k 10 500 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || die bench "$OUT/bench.err"
       python3 -c "import json,sys; d=json.load(open('$OUT/bench.json')); c=d.get('config4_zipf_update',{}); \
 print('bench', round(d['ms_per_step'],4), 'ms frac', round(d['roofline']['frac'],4), 'upd', round(c.get('update_exact_ms',0),3), \
 'split', round(c.get('update_split_ms',0),3), 'fp16', round(d.get('config3_fp16',{}).get('julia_f16_arith',{}).get('kernel_ms',0),4), \
 'cfg2_us', round(1e3*d.get('config2_gather',{}).get('kernel_ms',0),2))" ;;
     trace)
       timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof_bench" -o run --output-format csv \
-        -- python3 bench.py --steps 20 --warmup 3 --cpu-seconds 0 > "$OUT/bench_traced.json" \
+        -- python3 bench.py --full --steps 20 --warmup 3 --cpu-seconds 0 > "$OUT/bench_traced.json" \
         2> "$OUT/bench_traced.err" || die trace "$OUT/bench_traced.err"
       echo "trace ok" ;;
     tracehead)
