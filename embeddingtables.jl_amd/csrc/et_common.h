@@ -157,6 +157,18 @@ __device__ __forceinline__ T* col_ptr(const void* table, int64_t ld, int64_t col
     return (T*)table + row * (uint64_t)ld;
 }
 
+// The clamped entry range [lo, hi) of bag `bag` of a ragged index (1-based colptr over a
+// values buffer of capacity nnz): 0 <= lo <= hi <= nnz whatever colptr holds, so nothing is
+// ever read outside the buffer; *clamped = number of bounds that had to be moved.
+__device__ __forceinline__ void ragged_range(const int64_t* __restrict__ colptr, int64_t bag,
+                                             int64_t nnz, int64_t& lo, int64_t& hi,
+                                             int& clamped) {
+    const int64_t l = colptr[bag] - 1, h = colptr[bag + 1] - 1;
+    lo = l < 0 ? 0 : (l > nnz ? nnz : l);
+    hi = h < lo ? lo : (h > nnz ? nnz : h);
+    clamped = (lo != l ? 1 : 0) + (hi != h ? 1 : 0);
+}
+
 constexpr int kVecDims[] = {16, 32, 64, 128, 256, 512};
 
 inline bool vec_dim_ok(int D) {

@@ -1760,6 +1760,9 @@ int lookup_dispatch_convert(int dtype, int out_dtype, const et_lookup_desc* desc
     return fail(ET_ERR_UNSUPPORTED, "table dtype %d (conversions are between float types)", dtype);
 }
 
+// Variable-length bags (et_ragged_maplookup_prealloc): kernels and dispatch.
+#include "et_ragged.hip"
+
 }  // namespace et
 
 // ---------------------------------------------------------------------------
@@ -1844,6 +1847,15 @@ extern "C" int et_maplookup_prealloc_to(int dtype, int dst_dtype, const et_looku
         return et::lookup_dispatch(dtype, descs, ntables, batch, dst, ld_dst, flags, s);
     return et::lookup_dispatch_convert(dtype, dst_dtype, descs, ntables, batch, dst, ld_dst,
                                        flags, s);
+}
+
+extern "C" int et_ragged_maplookup_prealloc(int dtype, const et_ragged_desc* descs,
+                                            int32_t ntables, int64_t batch, void* dst,
+                                            int64_t ld_dst, uint32_t flags, void* stream) {
+    et::clear_err();
+    et::open_side_streams(static_cast<hipStream_t>(stream));
+    return et::ragged_dispatch(dtype, descs, ntables, batch, dst, ld_dst, flags,
+                               static_cast<hipStream_t>(stream));
 }
 
 ET_OOB_READER(lookup)

@@ -3803,6 +3803,9 @@ extern "C" int et_update_indexed(int dtype, void* table, int64_t ld_table,
 #undef ET_UI_T
 }
 
+// Ragged gradients (et_ragged_sgd, et_ragged_bag_ids): kernels and entry points.
+#include "et_ragged_update.hip"
+
 ET_OOB_READER(update)
 
 namespace et {

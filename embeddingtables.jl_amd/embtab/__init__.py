@@ -11,6 +11,7 @@ from ._lib import EmbtabError, check_errors
 from .tables import (AbstractEmbeddingTable, AbstractLookupType, ArgumentError, Dynamic,
                      Forward, IndexingContext, NoContext, SimpleEmbedding, SplitEmbedding, Static,
                      Update, columnpointer, example, featuresize)
+from .ragged import RaggedIndices
 from .lookup import (AbstractExecutionStrategy, DefaultStrategy, NoTangent,
                      PreallocationPlan, PreallocationStrategy, SimpleParallelStrategy, colwrap, destination, lookup,
                      lookup_, maplookup, maplookup_)
@@ -29,4 +30,5 @@ __all__ = [
     "rrule", "Descent", "AbstractIndexer", "Indexer", "SparseIndexer", "DenseIndexer",
     "IndexerView", "index_", "gettranslations", "update_", "optimise_update_",
     "ensemble_update", "PhasedUpdate", "EmbtabError", "check_errors",
+    "RaggedIndices",
 ]

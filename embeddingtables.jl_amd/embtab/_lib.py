@@ -64,6 +64,10 @@ EXPORTS = (
     "et_index_workspace_size",
     "et_index_build",
     "et_update_indexed",
+    "et_ragged_maplookup_prealloc",
+    "et_ragged_bag_ids",
+    "et_ragged_sgd_workspace_size",
+    "et_ragged_sgd",
     "et_concat_slabs",
     "et_split_slabs",
     "et_push_cols",
@@ -137,6 +141,42 @@ class UpdateDesc(ctypes.Structure):
     ]
 
 
+class RaggedDesc(ctypes.Structure):
+    """et_ragged_desc (include/embtab.h)."""
+
+    _fields_ = [
+        ("table", ctypes.c_void_p),
+        ("ld_table", ctypes.c_int64),
+        ("nrows", ctypes.c_int64),
+        ("dim", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("idx", ctypes.c_void_p),
+        ("nnz", ctypes.c_int64),
+        ("colptr", ctypes.c_void_p),
+        ("dst_row_off", ctypes.c_int64),
+        ("cols_per_page", ctypes.c_int64),
+    ]
+
+
+class RaggedUpdateDesc(ctypes.Structure):
+    """et_ragged_update_desc (include/embtab.h)."""
+
+    _fields_ = [
+        ("table", ctypes.c_void_p),
+        ("ld_table", ctypes.c_int64),
+        ("nrows", ctypes.c_int64),
+        ("dim", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("delta", ctypes.c_void_p),
+        ("ld_delta", ctypes.c_int64),
+        ("idx", ctypes.c_void_p),
+        ("nnz", ctypes.c_int64),
+        ("colptr", ctypes.c_void_p),
+        ("batch", ctypes.c_int64),
+        ("cols_per_page", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -175,6 +215,10 @@ def load() -> ctypes.CDLL:
         "et_index_build": ([vp, i32, i64, i64, i64, vp, vp, vp, vp, vp, i64, vp], c_int),
         "et_update_indexed": ([c_int, vp, i64, i64, i64, i32, vp, i64, vp, vp, i64, i64, vp, dbl, u32,
                                vp], c_int),
+        "et_ragged_maplookup_prealloc": ([c_int, vp, i32, i64, vp, i64, u32, vp], c_int),
+        "et_ragged_bag_ids": ([vp, i64, i64, vp, vp], c_int),
+        "et_ragged_sgd_workspace_size": ([vp, i32, vp], c_int),
+        "et_ragged_sgd": ([c_int, vp, i32, dbl, u32, vp, i64, vp], c_int),
         "et_concat_slabs": ([c_int, vp, i32, i64, i64, vp, vp, vp, i64, vp], c_int),
         "et_split_slabs": ([c_int, vp, i64, i64, i32, vp, vp, vp, i64, vp], c_int),
         "et_push_cols": ([c_int, vp, i64, i64, i64, i64, vp, i32, vp], c_int),

@@ -20,6 +20,7 @@ import threading
 import torch
 
 from . import _lib
+from .ragged import RaggedIndices, arithmetic_colptr
 from .tables import AbstractEmbeddingTable, ArgumentError, featuresize, example
 
 
@@ -73,6 +74,10 @@ def _check_table(A):
 
 
 def _check_idx(I: torch.Tensor) -> torch.Tensor:
+    if isinstance(I, RaggedIndices):
+        if not I.is_cuda:
+            raise ArgumentError("indices must be in device memory")
+        return I
     if not isinstance(I, torch.Tensor):
         raise TypeError("indices must be an int64 torch tensor")
     if I.dtype != torch.int64:
@@ -106,6 +111,8 @@ def _check_dst(dst: torch.Tensor, A, B: int):
 
 def _trailing_size(I: torch.Tensor) -> int:
     """src/lookup.jl:19: size(I, ndims(I)) — the batch (torch dim 0)."""
+    if isinstance(I, RaggedIndices):
+        return I.batch
     return int(I.shape[0])
 
 
@@ -137,6 +144,15 @@ def lookup_(dst: torch.Tensor, A: AbstractEmbeddingTable, I: torch.Tensor,
     D, R = A.size()
     flags = _lib.ET_FLAG_NONTEMPORAL if nontemporal else 0
     table, cpp = A.device_table()
+    if isinstance(I, RaggedIndices):
+        # variable-length bags: the ragged entry point with one table
+        descs = (_lib.RaggedDesc * 1)()
+        descs[0] = _lib.RaggedDesc(table, A.ld, R, D, 0, I.values.data_ptr(), I.nnz,
+                                   I.colptr.data_ptr(), 0, cpp)
+        _lib.check(L.et_ragged_maplookup_prealloc(_lib.et_dtype(dst), ctypes.addressof(descs), 1,
+                                                  B, dst.data_ptr(), _ld(dst), flags,
+                                                  _lib.stream_handle(dst.device)))
+        return dst
     if cpp:
         # paged table (SplitEmbedding): the descriptor entry point addresses pages
         descs = (_lib.LookupDesc * 1)()
@@ -217,6 +233,64 @@ def maplookup_(strategy: AbstractExecutionStrategy, dst, tables, I, nontemporal:
     return PreallocationPlan(strategy, dst, tables, Is, nontemporal, f16_fp32_acc)()
 
 
+def _fixed_descs(tables, Is, B: int, k: int, dtype):
+    """et_lookup_desc array of a list of fixed-pool (matrix or vector) indices."""
+    descs = (_lib.LookupDesc * len(tables))()
+    off = k
+    for t, (A, i) in enumerate(zip(tables, Is)):
+        _check_table(A)
+        _check_idx(i)
+        if A.dtype != dtype:
+            raise NotImplementedError(
+                f"table {t} eltype {A.dtype} != table 0 eltype {dtype}: one launch takes "
+                "tables of one element type")
+        if _trailing_size(i) != B:
+            raise ArgumentError(f"table {t}: batch {_trailing_size(i)} != {B}")
+        D, R = A.size()
+        pool = 1 if i.dim() == 1 else int(i.shape[1])
+        table, cpp = A.device_table()
+        descs[t] = _lib.LookupDesc(table, A.ld, R, D, pool, i.data_ptr(),
+                                   1 if i.dim() == 1 else _ld(i), off, cpp)
+        off += D
+    return descs
+
+
+def _ragged_descs(tables, Is, B: int, k: int, dtype):
+    """et_ragged_desc array for a list in which some table's indices are RaggedIndices: a
+    fixed-pool ``(B, P)`` matrix or a vector rides along as the ragged index it is, with the
+    arithmetic colptr ``1 + P * (0:B)`` (its bags must then be back to back: ``ld == P``).
+    Returns (descs, the synthesised colptr tensors to keep alive)."""
+    descs = (_lib.RaggedDesc * len(tables))()
+    keep = {}
+    off = k
+    for t, (A, i) in enumerate(zip(tables, Is)):
+        _check_table(A)
+        _check_idx(i)
+        if A.dtype != dtype:
+            raise NotImplementedError(
+                f"table {t} eltype {A.dtype} != table 0 eltype {dtype}: one launch takes "
+                "tables of one element type")
+        if _trailing_size(i) != B:
+            raise ArgumentError(f"table {t}: batch {_trailing_size(i)} != {B}")
+        D, R = A.size()
+        table, cpp = A.device_table()
+        if isinstance(i, RaggedIndices):
+            vals, nnz, colptr = i.values.data_ptr(), i.nnz, i.colptr
+        else:
+            P = 1 if i.dim() == 1 else int(i.shape[1])
+            if i.dim() == 2 and B > 1 and _ld(i) != P:
+                raise NotImplementedError(
+                    f"table {t}: a strided (B, P) index matrix (ld {_ld(i)} != P {P}) beside "
+                    "ragged indices; make it contiguous")
+            colptr = keep.get(P)
+            if colptr is None:
+                colptr = keep[P] = arithmetic_colptr(B, P, A.device)
+            vals, nnz = i.data_ptr(), B * P
+        descs[t] = _lib.RaggedDesc(table, A.ld, R, D, 0, vals, nnz, colptr.data_ptr(), off, cpp)
+        off += D
+    return descs, keep
+
+
 # Queue blocks of the per-XCD work-queue schedule (et_maplookup_prealloc_q), one per
 # (device, stream, thread): calls that share a block are ordered by their stream.  Zeroed once
 # on that stream when made; every launch leaves its block zero again.
@@ -266,23 +340,15 @@ class PreallocationPlan:
         if k + sum(featuresize(t) for t in tables) > dst.shape[1]:
             raise ArgumentError("destination has too few rows for prependrows + sum(D)")
         dtype = tables[0].dtype  # the tables' element type; dst may be another (U)
-        descs = (_lib.LookupDesc * len(tables))()
-        off = k
-        for t, (A, i) in enumerate(zip(tables, Is)):
-            _check_table(A)
-            _check_idx(i)
-            if A.dtype != dtype:
-                raise NotImplementedError(
-                    f"table {t} eltype {A.dtype} != table 0 eltype {dtype}: one launch takes "
-                    "tables of one element type")
-            if _trailing_size(i) != B:
-                raise ArgumentError(f"table {t}: batch {_trailing_size(i)} != {B}")
-            D, R = A.size()
-            pool = 1 if i.dim() == 1 else int(i.shape[1])
-            table, cpp = A.device_table()
-            descs[t] = _lib.LookupDesc(table, A.ld, R, D, pool, i.data_ptr(),
-                                       1 if i.dim() == 1 else _ld(i), off, cpp)
-            off += D
+        self._ragged = any(isinstance(i, RaggedIndices) for i in Is)
+        if self._ragged and dst.dtype != dtype:
+            raise NotImplementedError(
+                "PreallocationStrategy(k, eltype=U) with ragged indices: the ragged launch "
+                "writes the tables' element type")
+        if self._ragged:  # one fused et_ragged_maplookup_prealloc instead
+            descs, self._colptrs = _ragged_descs(tables, Is, B, k, dtype)
+        else:
+            descs = _fixed_descs(tables, Is, B, k, dtype)
         self._keep = (dst, tables, Is)  # the buffers the descriptors point into
         self._descs = descs
         self._n = len(tables)
@@ -300,7 +366,11 @@ class PreallocationPlan:
         """Launch on the current stream; returns the destination."""
         dst = self._dst
         stream = _lib.stream_handle(dst.device)
-        if self._src == self._dst_t:
+        if self._ragged:
+            _lib.check(self._lib.et_ragged_maplookup_prealloc(
+                self._src, ctypes.addressof(self._descs), self._n, self._B, dst.data_ptr(),
+                self._ld, self._flags, stream))
+        elif self._src == self._dst_t:
             q = _queue_block(dst.device, stream)
             _lib.check(self._lib.et_maplookup_prealloc_q(
                 self._src, ctypes.addressof(self._descs), self._n, self._B, dst.data_ptr(),

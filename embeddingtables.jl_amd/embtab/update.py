@@ -21,6 +21,7 @@ import torch
 from . import _lib
 from .lookup import (NoTangent, PreallocationStrategy, AbstractExecutionStrategy, colwrap,
                      lookup, maplookup, _ld, _check_idx)
+from .ragged import RaggedIndices
 from .tables import (AbstractEmbeddingTable, AbstractLookupType, ArgumentError, Dynamic,
                      featuresize, fused_update_path)
 
@@ -36,8 +37,9 @@ class SparseEmbeddingUpdate:
         self.indices = indices
 
     def __repr__(self):
+        I = self.indices
         return (f"SparseEmbeddingUpdate{{{self.lookup_type!r}}}(delta={tuple(self.delta.shape)}, "
-                f"indices={tuple(self.indices.shape)})")
+                f"indices={I if isinstance(I, RaggedIndices) else tuple(I.shape)})")
 
 
 def uncompress(x: SparseEmbeddingUpdate, dstcols: int | None = None,
@@ -45,6 +47,18 @@ def uncompress(x: SparseEmbeddingUpdate, dstcols: int | None = None,
     """Densify a sparse gradient into a ``(dstcols, D)`` tensor (src/sparseupdate.jl:16-32).
     A test helper in the reference; done with device tensor ops here."""
     I = x.indices
+    if isinstance(I, RaggedIndices):
+        # every entry's gradient column is its bag (0: the capacity tail, no bag)
+        bag = I.bag_ids()
+        nb = x.delta.shape[0] if maxindices is None else min(maxindices, x.delta.shape[0])
+        use = (bag > 0) & (bag <= nb)
+        cols, bag = I.values[use] - 1, bag[use] - 1
+        if dstcols is None:
+            dstcols = int(cols.max().item()) + 1 if cols.numel() else 0
+        dst = torch.zeros((dstcols, x.delta.shape[1]), dtype=x.delta.dtype,
+                          device=x.delta.device)
+        dst.index_add_(0, cols, x.delta[bag])
+        return dst
     if dstcols is None:
         dstcols = int(I.max().item())
     D = x.delta.shape[1]
@@ -187,6 +201,11 @@ class Indexer(AbstractIndexer):
         self._pending = (snap, int(maxindex))
         return snap
 
+    def _defer_ragged(self, indices: RaggedIndices, maxindex: int):
+        """The ragged counterpart of ``_defer``: the Indexer is built on first use from a copy
+        of the values and colptr taken now, in stream order (two device copies)."""
+        self._pending = (indices.clone(), int(maxindex))
+
     def _materialise(self):
         if self._pending is not None:
             indices, maxindex = self._pending
@@ -251,8 +270,20 @@ class IndexerView(AbstractIndexer):
 
 
 def index_(indexer: Indexer, A: torch.Tensor, maxindex: int) -> Indexer:
-    """``index!(indexer, A, maxindex)`` (src/utils.jl:306-314) on the device."""
+    """``index!(indexer, A, maxindex)`` (src/utils.jl:306-314) on the device.  For
+    RaggedIndices: the Indexer of the covered values as a vector index, with ``map`` (the
+    entry of every grouped occurrence) mapped through the entries' bags — the gradient
+    columns, so ``update_(table, grad, indexer, alpha)`` and IndexerView work as they are."""
     _check_idx(A)
+    if isinstance(A, RaggedIndices):
+        lo, hi = A.used_range()
+        index_(indexer, A.values[lo:hi], maxindex)
+        if hi > lo:
+            # an entry no bag covers exists only under an invalid colptr (the lookup counts
+            # it): it maps to bag 1 instead of reading outside the gradient
+            bag = A.bag_ids()[lo:hi].clamp_(min=1)
+            indexer.map = bag[indexer.map - 1]
+        return indexer
     B = int(A.shape[0])
     P = 1 if A.dim() == 1 else int(A.shape[1])
     n = B * P
@@ -335,6 +366,37 @@ def _update_desc(table: AbstractEmbeddingTable, grad: SparseEmbeddingUpdate) -> 
                            I.data_ptr(), 1 if I.dim() == 1 else _ld(I), B, cpp)
 
 
+def _ragged_update_desc(table: AbstractEmbeddingTable,
+                        grad: SparseEmbeddingUpdate) -> _lib.RaggedUpdateDesc:
+    R_ = _check_idx(grad.indices)
+    delta = grad.delta
+    if table.dtype not in _UPDATE_DTYPES or delta.dtype != table.dtype:
+        raise NotImplementedError(
+            f"update of a {table.dtype} table with a {delta.dtype} gradient (supported: "
+            "Float32 / Float64 / Float16 / BFloat16 tables with gradients of the same type)")
+    D, R = table.size()
+    if delta.dim() != 2 or delta.shape[0] != R_.batch or delta.shape[1] != D:
+        raise ArgumentError(f"gradient shape {tuple(delta.shape)} != ({R_.batch}, {D})")
+    if delta.numel() > 0 and delta.stride(1) != 1:
+        raise ArgumentError("gradient features must be contiguous")
+    tp, cpp = table.device_table()
+    return _lib.RaggedUpdateDesc(tp, table.ld, R, D, 0, delta.data_ptr(), _ld(delta),
+                                 R_.values.data_ptr(), R_.nnz, R_.colptr.data_ptr(), R_.batch,
+                                 cpp)
+
+
+def _ragged_sgd(descs, eta: float, flags: int, device, dtype, key: str = "ragged_sgd"):
+    """One et_ragged_sgd call over ragged gradients (always exact, caller's stream only)."""
+    L = _lib.load()
+    n = len(descs)
+    arr = (_lib.RaggedUpdateDesc * n)(*descs)
+    nb = ctypes.c_int64(0)
+    _lib.check(L.et_ragged_sgd_workspace_size(ctypes.addressof(arr), n, ctypes.byref(nb)))
+    ws = _workspace(nb.value, device, key)
+    _lib.check(L.et_ragged_sgd(_lib.TORCH_TO_ET[dtype], ctypes.addressof(arr), n, float(eta),
+                               flags, ws.data_ptr(), ws.numel(), _lib.stream_handle(device)))
+
+
 def _sparse_sgd(descs, eta: float, flags: int, device, dtype=torch.float32, snaps=None):
     """One et_sparse_sgd call; `snaps` (one device pointer or None per descriptor) makes it
     et_sparse_sgd_snap, whose key pass copies those tables' index arrays."""
@@ -387,7 +449,13 @@ def update_(*args, nontemporal: bool | None = None, exact: bool | None = None,
     use Julia's Float16 arithmetic unless ``f16_fp32_acc`` (sums in Float32).
     ``hot_pass=True`` (experimental, ET_FLAG_SGD_HOT_PASS) sums the longest occurrence
     lists of Float32 dim-128 tables bag-major (deterministic, not bit-identical to the
-    default split)."""
+    default split).
+
+    A gradient whose ``indices`` is a ``RaggedIndices`` (variable-length bags) goes through
+    et_ragged_sgd: always the exact serial sum whatever ``exact`` says (a hot column is one
+    serial chain on one wave), no hot pass.  In a multi-table call the ragged tables are
+    updated in one call per (path, eltype) group ahead of the others, which take the usual
+    path; a ``telemetry_cb`` runs after the ragged tables' update is enqueued."""
     if exact is None:
         exact = EXACT_DEFAULT
     if args and isinstance(args[0], Descent):
@@ -417,6 +485,16 @@ def _update_single(opt: Descent, table, grad: SparseEmbeddingUpdate, nontemporal
     the update from it.  The device pipeline indexes on its own; a caller-supplied Indexer is
     filled as the reference's is, from a snapshot of the indices the update's key pass takes
     (et_sparse_sgd_snap), built into the reference layout on first use (Indexer._defer)."""
+    if isinstance(grad.indices, RaggedIndices):
+        # ragged gradient: always the exact serial sum, whatever `exact` says; no hot pass
+        if isinstance(indexer, Indexer):
+            indexer._defer_ragged(grad.indices, table.size()[1])
+        if grad.indices.nnz == 0 or grad.indices.batch == 0:
+            return
+        _ragged_sgd([_ragged_update_desc(table, grad)], opt.eta,
+                    _sgd_flags(fused_update_path(table), nontemporal, False, exact,
+                               f16_fp32_acc), table.device, table.dtype)
+        return
     if grad.indices.numel() == 0:
         if isinstance(indexer, Indexer):
             indexer._pending = (grad.indices, int(table.size()[1]))
@@ -451,6 +529,32 @@ def _update_multi(opt: Descent, tables, grads, nontemporal: bool, exact: bool | 
         indexers = list(indexers)
         if len(indexers) != len(grads):
             raise ArgumentError("indexers and grads differ in length")
+    rag = [i for i, g in enumerate(grads) if isinstance(g.indices, RaggedIndices)]
+    if rag:
+        # a mixed list is split: the ragged tables in one et_ragged_sgd call per (path,
+        # eltype) group, ahead of the others, which take today's path unchanged
+        rgroups: dict = {}
+        for i in rag:
+            A, g = tables[i], grads[i]
+            if indexers is not None and isinstance(indexers[i], Indexer):
+                indexers[i]._defer_ragged(g.indices, A.size()[1])
+            if g.indices.nnz == 0 or g.indices.batch == 0:
+                continue
+            rgroups.setdefault((fused_update_path(A), A.dtype), []).append(
+                _ragged_update_desc(A, g))
+        ncall = 0
+        for (fused, dtype), descs in rgroups.items():
+            for c in range(0, len(descs), _lib.ET_MAX_TABLES_PER_LAUNCH):
+                _ragged_sgd(descs[c:c + _lib.ET_MAX_TABLES_PER_LAUNCH], opt.eta,
+                            _sgd_flags(fused, nontemporal, not fused, exact, f16_fp32_acc),
+                            tables[0].device, dtype, f"ragged_sgd{ncall}")
+                ncall += 1
+        rest = [i for i in range(len(grads)) if i not in set(rag)]
+        return _update_multi(opt, [tables[i] for i in rest], [grads[i] for i in rest],
+                             nontemporal, exact, f16_fp32_acc, num_splits, nthreads,
+                             scratchspaces, telemetry_cb,
+                             None if indexers is None else [indexers[i] for i in rest],
+                             hot_pass)
     # Group tables by the reference's per-table path: Static <= 512 B -> specialized
     # (Float32 eta, fused); otherwise generic with the unconverted Float64 eta
     # (src/sparseupdate.jl:232).
@@ -561,6 +665,9 @@ class PhasedUpdate:
         tables, grads = list(tables), list(grads)
         if len(tables) != len(grads):
             raise ArgumentError("tables and grads differ in length")
+        if any(isinstance(g.indices, RaggedIndices) for g in grads):
+            raise NotImplementedError("PhasedUpdate with a ragged gradient: et_ragged_sgd has "
+                                      "no phased form")
         groups: dict = {}
         for A, g in zip(tables, grads):
             if g.indices.numel() == 0:

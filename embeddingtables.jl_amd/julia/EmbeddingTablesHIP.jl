@@ -582,6 +582,121 @@ function update!(opt::Flux.Descent, tables::AbstractVector{<:HipTable},
 end
 
 #####
+##### Variable-length bags (no counterpart in the reference, whose pooled lookup takes a
+##### dense P x B matrix): `values` and `colptr` are the rowval / colptr of a SparseMatrixCSC
+##### pattern, on the device.  The pooled sum is src/lookup.jl:134-147 per bag, the update the
+##### serial per-column sum of src/sparseupdate.jl:97-129 over the expanded gradient.
+#####
+
+struct RaggedIndices
+    values::HipVector{Int}   # every bag's indices back to back; its length is a CAPACITY
+    colptr::HipVector{Int}   # batch + 1 entries, 1-based, non-decreasing
+end
+batchsize(R::RaggedIndices) = length(R.colptr) - 1
+Base.isempty(R::RaggedIndices) = isempty(R.values) || batchsize(R) == 0
+
+struct RaggedDesc
+    table::Ptr{Cvoid}
+    ld_table::Int64
+    nrows::Int64
+    dim::Int32
+    reserved::Int32
+    idx::Ptr{Int64}
+    nnz::Int64
+    colptr::Ptr{Int64}
+    dst_row_off::Int64
+    cols_per_page::Int64
+end
+
+struct RaggedUpdateDesc
+    table::Ptr{Cvoid}
+    ld_table::Int64
+    nrows::Int64
+    dim::Int32
+    reserved::Int32
+    delta::Ptr{Cvoid}
+    ld_delta::Int64
+    idx::Ptr{Int64}
+    nnz::Int64
+    colptr::Ptr{Int64}
+    batch::Int64
+    cols_per_page::Int64
+end
+
+function _ragged_desc(A::HipTable, R::RaggedIndices, off)
+    tp, ldt, cpp = _device_table(A)
+    return RaggedDesc(tp, ldt, size(A, 2), size(A, 1), 0, R.values.ptr, length(R.values),
+                      R.colptr.ptr, off, cpp)
+end
+
+function _ragged_maplookup(::Type{T}, descs::Vector{RaggedDesc}, batch, p, ld) where {T}
+    check(ccall((:et_ragged_maplookup_prealloc, libembtab), Cint,
+                (Cint, Ptr{RaggedDesc}, Int32, Int64, Ptr{Cvoid}, Int64, UInt32, Ptr{Cvoid}),
+                et_dtype(T), descs, length(descs), batch, p, ld, ET_FLAG_NONTEMPORAL, stream()))
+end
+
+function lookup!(dst, A::HipTable{S,T}, R::RaggedIndices) where {S,T}
+    p, ld = _ptr_ld(dst)
+    _ragged_maplookup(T, [_ragged_desc(A, R, 0)], batchsize(R), p, ld)
+    return dst
+end
+
+# every table's indices ragged: ONE fused launch
+function maplookup!(strategy::PreallocationStrategy, dst::HipMatrix{T},
+                    x::Vector{<:HipTable{<:Any,T}}, I::Vector{RaggedIndices}; kw...) where {T}
+    descs = Vector{RaggedDesc}(undef, length(x))
+    off = strategy.prependrows
+    for (t, (A, R)) in enumerate(zip(x, I))
+        descs[t] = _ragged_desc(A, R, off)
+        off += size(A, 1)
+    end
+    _ragged_maplookup(T, descs, batchsize(first(I)), dst.ptr, leading(dst))
+    return dst
+end
+
+# the gradient column (bag, 1-based) of every entry; 0 for the capacity tail
+function bag_ids(R::RaggedIndices)
+    bag = HipArray{Int}(undef, length(R.values))
+    check(ccall((:et_ragged_bag_ids, libembtab), Cint,
+                (Ptr{Int64}, Int64, Int64, Ptr{Int64}, Ptr{Cvoid}),
+                R.colptr.ptr, batchsize(R), length(R.values), bag.ptr, stream()))
+    return bag
+end
+
+function _ragged_sgd(::Type{T}, descs::Vector{RaggedUpdateDesc}, eta::Float64,
+                     flags::UInt32) where {T}
+    nb = Ref{Int64}(0)
+    check(ccall((:et_ragged_sgd_workspace_size, libembtab), Cint,
+                (Ptr{RaggedUpdateDesc}, Int32, Ref{Int64}), descs, length(descs), nb))
+    ws = _workspace(nb[], -2)
+    check(ccall((:et_ragged_sgd, libembtab), Cint,
+                (Cint, Ptr{RaggedUpdateDesc}, Int32, Float64, UInt32, Ptr{Cvoid}, Int64,
+                 Ptr{Cvoid}),
+                et_dtype(T), descs, length(descs), eta, flags, ws.ptr, length(ws), stream()))
+end
+
+# A ragged gradient: delta (D x batch) and the RaggedIndices of the forward lookup.  Always
+# the exact serial sum (et_ragged_sgd never splits a column).
+struct RaggedEmbeddingUpdate{D}
+    delta::D
+    indices::RaggedIndices
+end
+
+function update!(opt::Flux.Descent, table::HipTable{S,T}, grad::RaggedEmbeddingUpdate,
+                 ::Val{Nontemporal} = Val(true)) where {S,T<:UpdateEltype,Nontemporal}
+    isempty(grad.indices) && return nothing
+    flags = (Nontemporal ? ET_FLAG_NONTEMPORAL : UInt32(0)) |
+            (_fused(table) ? UInt32(0) : ET_FLAG_SGD_UNFUSED)
+    dp, dld = _ptr_ld(grad.delta)
+    tp, ldt, cpp = _device_table(table)
+    R = grad.indices
+    desc = RaggedUpdateDesc(tp, ldt, size(table, 2), size(table, 1), 0, dp, dld, R.values.ptr,
+                            length(R.values), R.colptr.ptr, batchsize(R), cpp)
+    _ragged_sgd(T, [desc], Float64(opt.eta), flags)
+    return nothing
+end
+
+#####
 ##### Sharded Preallocation maplookup over the GPUs of a node (BASELINE config 5):
 ##### one Julia process per GPU, RCCL over xGMI (include/embtab.h, csrc/et_shard.cpp)
 #####
@@ -682,6 +797,6 @@ end
 
 export HipEmbedding, HipSplitEmbedding, HipArray, HipVector, HipMatrix, EmbtabError,
     DeviceColumns, HipIndexer, ShardedPreallocation, shard_plan, comm_id, comm_init,
-    comm_destroy, comm_loopback
+    comm_destroy, comm_loopback, RaggedIndices, RaggedEmbeddingUpdate, bag_ids
 
 end # module

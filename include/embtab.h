@@ -273,6 +273,99 @@ int et_index_build(const int64_t* idx, int32_t pool, int64_t ld_idx, int64_t bat
                    int64_t* map, int64_t* nunique_dev, void* workspace, int64_t ws_bytes,
                    void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Variable-length (ragged) bags.  The reference has no ragged form: its pooled lookup
+ * takes a dense P x B index matrix.  These entries extend its pooled sum
+ * (src/lookup.jl:134-147) and its per-column serial gradient sum
+ * (src/sparseupdate.jl:97-129) to bags of any length, given as the pattern of a Julia
+ * SparseMatrixCSC: `idx` is rowval (the indices of all bags, back to back) and `colptr`
+ * has batch + 1 entries, Int64 and 1-BASED, non-decreasing; bag j (0-based) owns
+ * idx[colptr[j]-1 .. colptr[j+1]-2].
+ *
+ * `nnz` is the CAPACITY of idx, not the number of entries in use: the kernels find a bag
+ * from colptr alone and use nnz only to clamp, so idx and colptr may be refilled in place
+ * (also under a captured HIP graph) with any total length that fits.  Nothing is ever read
+ * outside idx[0 .. nnz): each bag's lo = colptr[j]-1 and hi = colptr[j+1]-1 are clamped to
+ * 0 <= lo <= hi <= nnz, and every bound that needed clamping counts one out-of-range event
+ * (et_check_errors), as an index outside 1..nrows does.
+ * ------------------------------------------------------------------------------- */
+
+/* One table of a ragged lookup. */
+typedef struct et_ragged_desc {
+    const void* table;     /* as in et_lookup_desc */
+    int64_t ld_table;
+    int64_t nrows;
+    int32_t dim;
+    int32_t reserved;      /* 0 */
+    const int64_t* idx;    /* device, the bags' indices back to back, 1-based Int64 */
+    int64_t nnz;           /* entries addressable at idx (a capacity, see above) */
+    const int64_t* colptr; /* device, batch + 1 entries, 1-based, non-decreasing */
+    int64_t dst_row_off;   /* as in et_lookup_desc */
+    int64_t cols_per_page; /* as in et_lookup_desc */
+} et_ragged_desc;
+
+/* Fused ragged lookup + concat: for every table t and bag j,
+ *   dst[desc[t].dst_row_off + (0:dim_t-1), j] = table_t[:, idx_t[lo]]            (a COPY)
+ *                                               + table_t[:, idx_t[lo+1]] + ...  (in order)
+ * with [lo, hi) the bag's clamped range; an empty bag writes zero(T) (+0.0).  The sum starts
+ * from a copy of the first row and adds the others one at a time in index order, as
+ * lookup_static_inner does (src/lookup.jl:134-147), in the accumulator type of
+ * et_pooled_sum (ET_FLAG_F16_FP32_ACC; BF16 in fp32 rounded once), so a bag of length L
+ * equals et_pooled_sum of that bag with pool = L bit for bit, and a one-entry bag on a row
+ * of -0.0 gives -0.0.  An index outside 1..nrows adds a zero row and is counted.
+ * ntables <= ET_MAX_TABLES_PER_LAUNCH; a single-table ragged lookup is ntables = 1.
+ * batch == 0 is a no-op.  Honours ET_FLAG_NONTEMPORAL on the stores. */
+int et_ragged_maplookup_prealloc(int dtype, const et_ragged_desc* descs, int32_t ntables,
+                                 int64_t batch, void* dst, int64_t ld_dst, uint32_t flags,
+                                 void* stream);
+
+/* bag[k] = 1-based bag of entry k for k in 0..nnz-1, or 0 if k lies outside
+ * [colptr[0]-1, colptr[batch]-1) (the capacity tail); bounds clamped as above.  The gradient
+ * column of every entry: what `map` of an Indexer built over the values (et_index_build with
+ * pool = 1) is mapped through to give the reference-layout Indexer of ragged indices
+ * (src/utils.jl:306-314). */
+int et_ragged_bag_ids(const int64_t* colptr, int64_t batch, int64_t nnz, int64_t* bag,
+                      void* stream);
+
+/* One table of a ragged sparse-SGD update. */
+typedef struct et_ragged_update_desc {
+    void* table;           /* device pointer, updated in place */
+    int64_t ld_table;
+    int64_t nrows;
+    int32_t dim;
+    int32_t reserved;      /* 0 */
+    const void* delta;     /* dim x batch gradient, column j at delta + j*ld_delta */
+    int64_t ld_delta;
+    const int64_t* idx;    /* the values of the forward lookup */
+    int64_t nnz;           /* capacity of idx */
+    const int64_t* colptr; /* batch + 1 entries */
+    int64_t batch;
+    int64_t cols_per_page; /* as in et_lookup_desc */
+} et_ragged_update_desc;
+
+/* Bytes of device workspace et_ragged_sgd needs for these descriptors (grows with the sum
+ * of nnz; any alignment, as et_sgd_workspace_size). */
+int et_ragged_sgd_workspace_size(const et_ragged_update_desc* descs, int32_t ntables,
+                                 int64_t* bytes);
+
+/* Sparse SGD over ragged gradients — et_sparse_sgd where entry k of a table belongs to bag
+ * bag(k) (et_ragged_bag_ids) instead of bag k / pool:
+ *   for every table t and every distinct column r among the entries with bag(k) != 0:
+ *     acc = +0 ; for each such entry k with idx[k] == r, in INCREASING k: acc += delta_t[:, bag(k)]
+ *     table_t[:, r] = the update of et_sparse_sgd (fused, ET_FLAG_SGD_UNFUSED,
+ *                     ET_FLAG_SGD_F64_ALPHA)
+ * — the reference's serial per-column sum (src/sparseupdate.jl:97-129) over the expanded
+ * gradient, so the result equals a vector-index et_sparse_sgd of delta[:, bag(k)] bit for bit.
+ * A column with no participating entry is not written; entries of the capacity tail
+ * contribute nothing.  Always exact: no column is ever split (ET_FLAG_EXACT_UPDATE and
+ * ET_FLAG_EXACT_IF_FAST are accepted and ignored), so a hot column is one serial chain on one
+ * wave.  ET_F32 / ET_F64 / ET_F16 (both accumulation modes) / ET_BF16.
+ * ET_FLAG_SGD_INDEX_ONLY, ET_FLAG_SGD_APPLY_ONLY and ET_FLAG_SGD_HOT_PASS return
+ * ET_ERR_UNSUPPORTED.  Stream-ordered on the caller's stream only (no side streams, no host
+ * synchronisation).  The sum of nnz must be below 2^31 - 1. */
+int et_ragged_sgd(int dtype, const et_ragged_update_desc* descs, int32_t ntables, double eta,
+                  uint32_t flags, void* workspace, int64_t ws_bytes, void* stream);
+
 /* Assemble the Preallocation concat from per-rank slabs after an all-gather
  * (table-wise sharding across GPUs, no counterpart in the single-process
  * reference): slab r is a (slab_ld x batch) column-major block at
