@@ -117,28 +117,6 @@ __global__ __launch_bounds__(256) void k_ragged_apply(
     }
 }
 
-template <typename T, typename C>
-int launch_ragged_apply(const UpdatePack& pack, int ntables, const Grouped& gr, const UpdateWs& w,
-                        const uint32_t* bag_ids, int64_t n, uint32_t sent, double eta_c,
-                        double eta, int mode, bool nt, hipStream_t s) {
-    const int64_t nb = cdiv64(n, 4);
-    const unsigned grid = (unsigned)(nb < 16384 ? nb : 16384);
-#define ET_RA(M, NTV)                                                                        \
-    hipLaunchKernelGGL((k_ragged_apply<T, C, M, NTV>), dim3(grid), dim3(256), 0, s, pack,     \
-                       ntables, gr.keys, gr.vals, w.seg_start, w.counters, bag_ids, sent,     \
-                       (C)eta_c, eta)
-    if (mode == 0) {
-        if (nt) ET_RA(0, true); else ET_RA(0, false);
-    } else if (mode == 1) {
-        if (nt) ET_RA(1, true); else ET_RA(1, false);
-    } else {
-        if (nt) ET_RA(2, true); else ET_RA(2, false);
-    }
-#undef ET_RA
-    ET_LAUNCH_CHECK("k_ragged_apply");
-    return ET_OK;
-}
-
 struct RaggedWs {
     UpdateWs u;
     uint32_t* bag;  // bag id of every entry, tables back to back
@@ -147,7 +125,7 @@ struct RaggedWs {
 
 inline RaggedWs carve_ragged_ws(char* base, int64_t n) {
     RaggedWs w;
-    w.u = carve_update_ws(base, n, 0, kChunk);
+    w.u = plan_index_ws(base, n);
     w.bag = base ? reinterpret_cast<uint32_t*>(base + w.u.bytes) : nullptr;
     w.bytes = w.u.bytes + align256(4 * (n + 1));
     return w;
@@ -274,18 +252,16 @@ extern "C" int et_ragged_sgd(int dtype, const et_ragged_update_desc* descs, int3
     rc = et::group_occurrences(pack, ntables, n, sent, et::kChunk, w.u, gr, s);
     if (rc != ET_OK) return rc;
 
-    const bool nt = (flags & ET_FLAG_NONTEMPORAL) != 0;
-    const int mode = (flags & ET_FLAG_SGD_UNFUSED) ? ((flags & ET_FLAG_SGD_F64_ALPHA) ? 2 : 1) : 0;
     const double eta_c = et::convert_eta(dtype, eta);
-#define ET_RA_T(T, C) \
-    return et::launch_ragged_apply<T, C>(pack, ntables, gr, w.u, w.bag, n, sent, eta_c, eta, mode, nt, s)
-    switch (dtype) {
-        case ET_F32: ET_RA_T(float, float);
-        case ET_F64: ET_RA_T(double, double);
-        case ET_BF16: ET_RA_T(__bf16, float);
-        default:
-            if (flags & ET_FLAG_F16_FP32_ACC) ET_RA_T(_Float16, float);
-            ET_RA_T(_Float16, _Float16);
-    }
-#undef ET_RA_T
+    const int64_t nb = et::cdiv64(n, 4);
+    const unsigned grid = (unsigned)(nb < 16384 ? nb : 16384);
+    return et::dispatch_sgd(dtype, flags, [&](auto e, auto mode, auto nt) {
+        using T = typename decltype(e)::type;
+        using C = typename decltype(e)::acc;
+        hipLaunchKernelGGL((et::k_ragged_apply<T, C, decltype(mode)::value, decltype(nt)::value>),
+                           dim3(grid), dim3(256), 0, s, pack, ntables, gr.keys, gr.vals,
+                           w.u.seg_start, w.u.counters, w.bag, sent, (C)eta_c, eta);
+        ET_LAUNCH_CHECK("k_ragged_apply");
+        return (int)ET_OK;
+    });
 }

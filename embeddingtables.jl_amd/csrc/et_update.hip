@@ -7,20 +7,42 @@
 //   _update_specialized_impl! / _update_generic_impl!                 src/sparseupdate.jl:57-154
 //   multi-table update!(opt, tables, grads, indexers; num_splits)     src/sparseupdate.jl:199-238
 //
-// Pipeline (all stream-ordered, no host synchronisation):
+// Pipeline of et_sparse_sgd (all stream-ordered, no host synchronisation).
+// Index phase (group_occurrences; all an ET_FLAG_SGD_INDEX_ONLY call runs):
 //   1. k_build_keys   occurrence o of table t -> key = row_off[t] + (col - 1), value = o
 //                      (o enumerates (table, bag, entry) with the entry fastest — the
 //                      reference's `columns(A)` order, src/utils.jl:69-86)
 //   2. radix sort      stable, so equal keys keep occurrence order (= remap! order)
 //   3. segments        run boundaries of equal keys -> distinct (table, column) pairs
-//   4. chunks          each segment is cut into chunks of at most kChunk occurrences
-//                      (unless ET_FLAG_EXACT_UPDATE), so a Zipf-hot column cannot
-//                      serialise one wave for milliseconds
-//   5. k_sgd_chunks    one lane group per chunk: acc = +0; acc += delta[:, bag] in
-//                      order; single-chunk segments apply the update directly,
-//                      others write a partial row
-//   6. k_sgd_combine   multi-chunk segments: acc = +0; acc += partial[p] in chunk order;
-//                      apply the update
+//   4. chunks          each segment is cut into chunks of at most `chunk` occurrences, one
+//                      ChunkRec each, so a Zipf-hot column cannot serialise one wave for
+//                      milliseconds; multi-chunk segments are also listed (mlist)
+//   4h. hot pick       split mode with ET_FLAG_SGD_HOT_PASS: the longest columns of the
+//                      hot-shaped tables are retired from the records and the list
+//                      (k_hot_hist, k_hot_pick, k_hot_slots)
+// Update phase, split mode (the default; launch_sgd_typed), on the caller's stream:
+//   5h. k_sgd_hot, k_hot_combine   the retired hot columns, summed bag-major
+//   5. k_sgd_chunks5  per capacity group, one lane group per chunk of more than one
+//                      occurrence: acc = +0; acc += delta[:, bag] in order; single-chunk
+//                      segments apply the update, the others write a partial row
+//   6. k_sgd_tail     per capacity group, one launch: its first workgroups combine the
+//                      multi-chunk segments (acc = +0; acc += partial[p] in a fixed
+//                      partition; apply), the rest update the single-occurrence columns
+//   7. k_sgd_chunks_generic, k_sgd_combine_generic   the same two steps for tables off the
+//                      vector path (any element type, dim or alignment)
+// Update phase, exact mode (ET_FLAG_EXACT_UPDATE / _IF_FAST; launch_sgd_exact[_generic]):
+// a column of at most kExactChunk occurrences is one chunk, a longer one a serial chain.
+//   side streams      the early plans from the index arrays, from the start of the call
+//                      (launch_ec_plan: k_eh_pick, k_ec_count .. k_ec_emit); the regular
+//                      plan over the multi-chunk list once the chunk records exist
+//                      (launch_chain_plan: k_chain_tile_count .. k_chain_emit); then the
+//                      three chain lists (k_sgd_chains_x early, k_sgd_chains regular),
+//                      all joined back into the caller's stream before the call returns
+//   caller's stream   k_sgd_exact per capacity group (the chunk pass over single-chunk
+//                      columns and the singles in one launch), k_sgd_chunks_generic for the
+//                      other tables' single-chunk columns; no partial sums, no combine
+// A batch of 2^27 bags or more has no chains: every column is one chunk of steps 5-7.
+//
 // The update of one column is  w = fma(-eta, acc, w)  (fused, the specialized path)
 // or  w = w - eta*acc  (unfused, the generic path; optionally evaluated in Float64 as
 // the reference's multi-table generic path does), chosen by ET_FLAG_SGD_UNFUSED /
@@ -28,6 +50,7 @@
 #include <algorithm>
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "et_common.h"
 #include "et_chain_asm.h"
@@ -310,7 +333,7 @@ __global__ __launch_bounds__(256) void k_chunk_records_multi(
     }
 }
 
-// 5./6. gradient sums and the update ---------------------------------------------
+// Gradient sums and the update -----------------------------------------------------
 
 template <int MODE>  // 0 fused fma, 1 unfused f32, 2 unfused f64 alpha
 __device__ __forceinline__ float sgd_apply(float w, float acc, float eta32, double eta64) {
@@ -514,7 +537,7 @@ __device__ __forceinline__ void sgd_chunks_body(
         const uint64_t left = ((uint64_t)C - wid + nwaves - 1) / nwaves - (uint64_t)it * 64u;
         uint32_t nq = left < 64u ? (uint32_t)left : 64u;
         if (skip_singles) {
-            // the records this pass walks (not k_sgd_singles', nor the exact mode's chains:
+            // the records this pass walks (not sgd_singles_body's, nor the exact mode's chains:
             // the chunks of multi-chunk columns), compacted to the front
             const bool keep = valid && m_key != sent && !(m_dst == kApply && m_s1 - m_s0 == 1u) &&
                               !(skip_multi && m_dst != kApply);
@@ -567,27 +590,20 @@ __device__ __forceinline__ void sgd_chunks_body(
     }
 }
 
-#define ET_SGD_CHUNKS_ARGS                                                                     \
-    UpdatePack pack, int ntables, const uint32_t* __restrict__ keys,                           \
-        const uint32_t* __restrict__ vals, const ChunkRec* __restrict__ recs,                  \
-        const uint32_t* __restrict__ counters, float* __restrict__ partials, int pdim,         \
-        uint32_t sent, float eta32, double eta64, uint32_t my_mask, int skip_singles
-template <int D, int MODE, bool NT>
-__global__ __launch_bounds__(256) void k_sgd_chunks(ET_SGD_CHUNKS_ARGS) {
-    sgd_chunks_body<D, MODE, NT>(pack, ntables, keys, vals, recs, counters, partials, pdim, sent,
-                                 eta32, eta64, my_mask, skip_singles, 0, blockIdx.x, gridDim.x);
-}
-// The same pass compiled for 5 waves per SIMD (96 VGPRs instead of 97-104: 4 waves).
+// The chunk pass compiled for 5 waves per SIMD (96 VGPRs; left to itself the compiler takes
+// 97-104: 4 waves — that 4-wave twin was the slower one and is gone).
 template <int D, int MODE, bool NT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k_sgd_chunks5(
-    ET_SGD_CHUNKS_ARGS) {
+    UpdatePack pack, int ntables, const uint32_t* __restrict__ keys,
+    const uint32_t* __restrict__ vals, const ChunkRec* __restrict__ recs,
+    const uint32_t* __restrict__ counters, float* __restrict__ partials, int pdim, uint32_t sent,
+    float eta32, double eta64, uint32_t my_mask, int skip_singles) {
     sgd_chunks_body<D, MODE, NT>(pack, ntables, keys, vals, recs, counters, partials, pdim, sent,
                                  eta32, eta64, my_mask, skip_singles, 0, blockIdx.x, gridDim.x);
 }
-#undef ET_SGD_CHUNKS_ARGS
 
 // Single-occurrence columns (70% of the chunks on the config-4 batch, 1.34 M of 2.0 M):
-// in k_sgd_chunks each is a chain of dependent loads (record -> occurrence id -> Δ
+// in the chunk pass each is a chain of dependent loads (record -> occurrence id -> Δ
 // column and table column -> store) walked one chunk per lane group at a time, so the
 // pass waits on memory latency.  Here a wave takes the same 64 records at a time, keeps
 // the singles (compacted to the front with a lane permute), and each lane group updates
@@ -810,27 +826,6 @@ __device__ __forceinline__ void sgd_combine_body(
             __syncthreads();
         }
     }
-}
-
-template <int D, int MODE, bool NT>
-__global__ __launch_bounds__(256) void k_sgd_singles(
-    UpdatePack pack, int ntables, const uint32_t* __restrict__ vals,
-    const ChunkRec* __restrict__ recs, const uint32_t* __restrict__ counters, uint32_t sent,
-    float eta32, double eta64, uint32_t my_mask) {
-    sgd_singles_body<D, MODE, NT>(pack, ntables, vals, recs, counters, sent, eta32, eta64,
-                                  my_mask, blockIdx.x, gridDim.x);
-}
-
-template <int D, int MODE, bool NT>
-__global__ __launch_bounds__(256) void k_sgd_combine(
-    UpdatePack pack, int ntables, const uint32_t* __restrict__ keys,
-    const uint32_t* __restrict__ seg_start, const uint32_t* __restrict__ partial_start,
-    const uint32_t* __restrict__ counters, const uint32_t* __restrict__ mlist,
-    const float* __restrict__ partials, int pdim, uint32_t sent, float eta32, double eta64,
-    uint32_t my_mask) {
-    sgd_combine_body<D, MODE, NT>(pack, ntables, keys, seg_start, partial_start, counters, mlist,
-                                  partials, pdim, sent, eta32, eta64, my_mask, blockIdx.x,
-                                  gridDim.x);
 }
 
 // The combine and the singles in one launch: the first `ncomb` workgroups combine, the
@@ -1580,10 +1575,11 @@ __global__ __launch_bounds__(256) void k_chain_emit(UpdatePack pack, int ntables
     }
 }
 
-// Debug check of the chain plan (ET_CHAIN_CHECK=1): every entry of every chain addresses
-// a gradient column of its table's batch with at most S adds, the entries carrying
-// adds number exactly E and precede the padding; a violation is counted in the device
-// error word (et_check_errors) as 1 << 20 and the entry neutralised to 0.
+#ifdef ET_EXPERIMENTS
+// Debug check of the chain plan (experiment builds, ET_CHAIN_CHECK=1): every entry of every
+// chain addresses a gradient column of its table's batch with at most S adds, the entries
+// carrying adds number exactly E and precede the padding; a violation is counted in the
+// device error word (et_check_errors) as 1 << 20 and the entry neutralised to 0.
 __global__ __launch_bounds__(256) void k_chain_check(UpdatePack pack, int ntables,
                                                      const uint32_t* __restrict__ counters,
                                                      const uint32_t* __restrict__ cnt,
@@ -1624,6 +1620,7 @@ __global__ __launch_bounds__(256) void k_chain_check(UpdatePack pack, int ntable
         if (lane == 0 && (bad || real != info[m].y)) note_oob(1 << 20);
     }
 }
+#endif  // ET_EXPERIMENTS
 
 // Early chains.  The longest chains of a Zipf batch belong to the smallest tables (the
 // 3-row Criteo table's hottest column has 835 K occurrences: a ~3 ms chain), and a chain
@@ -2321,19 +2318,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
                                 quad_min, list);
 }
 
-// Eight chain waves per workgroup (two per SIMD; one workgroup per CU by the LDS
-// reservation): for latency-bound lists (the early hot columns' S = 1 quad walks spend about a
-// third of their cycles issuing), so one CU keeps twice the gradient loads in flight.
-template <typename T, typename C, int MODE, bool NT>
-__global__ __launch_bounds__(512) void k_sgd_chains_w(
-    UpdatePack pack, int ntables, uint32_t* __restrict__ counters,
-    const ChainCol* __restrict__ chains, const uint32_t* __restrict__ order,
-    ChainEnt ce, int ns, C eta_c, double eta64, uint32_t quad_min,
-    uint32_t list) {
-    chain_items<T, C, MODE, NT>(pack, ntables, counters, chains, order, ce, ns, eta_c, eta64,
-                                quad_min, list);
-}
-
 // The same chain loop on SIMDs of its own: the kernel writes a255, so it is allocated the
 // whole accumulation-register file besides its VGPRs and no other wave — of the chunk pass,
 // the singles, the index phase — can be resident on its SIMDs while it runs; the chain waves
@@ -2421,7 +2405,7 @@ __global__ __launch_bounds__(256) void k_sgd_combine_generic(
         const int t = table_of_key(pack, ntables, key);
         const et_update_desc& d = pack.d[t];
         if ((pack.vec_mask >> t) & 1u) continue;
-        // the vector combine's fixed partition (k_sgd_combine: 8 contiguous ranges of
+        // the vector combine's fixed partition (sgd_combine_body: 8 contiguous ranges of
         // partials, each summed from 0, the range sums added in order), so a table taking
         // the generic path combines exactly like a vector-width feature slice of it
         const uint32_t np = p1 - p0;
@@ -2443,6 +2427,65 @@ __global__ __launch_bounds__(256) void k_sgd_combine_generic(
 // ---------------------------------------------------------------------------
 // Workspace
 // ---------------------------------------------------------------------------
+
+// Tables the hot-column pass can take (the workspace is sized for all of them).
+inline bool hot_shape(const et_update_desc& d) {
+    return d.dim == 128 && d.pool >= 1 && d.pool <= kHotMaxPool && d.batch > 0;
+}
+
+// Hot-shaped tables: their count, largest batch, and slot-byte offsets (soff[t]) / total.
+struct HotSizes {
+    int n;
+    int64_t batch, bytes;
+    uint64_t soff[ET_MAX_TABLES_PER_LAUNCH];
+};
+
+inline HotSizes hot_sizes(const et_update_desc* descs, int ntables) {
+    HotSizes h{};
+    for (int t = 0; t < ntables; ++t)
+        if (hot_shape(descs[t])) {
+            ++h.n;
+            if (descs[t].batch > h.batch) h.batch = descs[t].batch;
+            h.soff[t] = (uint64_t)h.bytes;
+            h.bytes += descs[t].batch * ((descs[t].pool + 3) & ~3);
+        }
+    return h;
+}
+
+// Early-chain tables of these descriptors (ec_table) and their occurrences; the list
+// sizes the workspace whatever the flags, and et_sparse_sgd uses it in exact Float32 mode.
+// hot = true: the big tables' hot-column list (eh_table, kEhK slots each; empty unless ET_EH).
+inline EcList ec_list(const et_update_desc* descs, int ntables, int64_t* occ, bool hot = false) {
+    EcList ec;
+    ec.n = 0;
+    ec.mask = 0;
+    ec.hot = hot ? 1 : 0;
+    ec.blk0[0] = ec.col0[0] = ec.cb0[0] = 0;
+    *occ = 0;
+    if (hot && !eh_enabled()) return ec;
+    for (int t = 0; t < ntables; ++t) {
+        const et_update_desc& d = descs[t];
+        if (hot ? !eh_table(d) : !ec_table(d)) continue;
+        const uint32_t nb = (uint32_t)cdiv64(d.batch, kEcBags);
+        const uint32_t cols = hot ? (uint32_t)kEhK : (uint32_t)d.nrows;
+        ec.t[ec.n] = t;
+        ec.mask |= 1u << t;
+        ec.blk0[ec.n + 1] = ec.blk0[ec.n] + nb;
+        ec.col0[ec.n + 1] = ec.col0[ec.n] + cols;
+        ec.cb0[ec.n + 1] = ec.cb0[ec.n] + nb * cols;
+        *occ += d.pool * d.batch;
+        ++ec.n;
+    }
+    return ec;
+}
+
+inline EhMap eh_map(const EcList& eh) {
+    EhMap m;
+    m.mask = eh.hot ? eh.mask : 0u;
+    for (int t = 0; t < ET_MAX_TABLES_PER_LAUNCH; ++t) m.e[t] = 0;
+    for (int e = 0; e < eh.n && eh.hot; ++e) m.e[eh.t[e]] = (int8_t)e;
+    return m;
+}
 
 struct UpdateWs {
     uint32_t *ka, *va, *kb, *vb, *hist, *part, *seg_start, *nch, *multi, *counters,
@@ -2499,11 +2542,13 @@ inline int64_t chain_tiles_max(int64_t n, uint32_t chunk) {
 }
 
 // Lay out (or size, when base == nullptr) the update workspace for n occurrences and
-// partial rows of pdim floats.
-inline UpdateWs carve_update_ws(char* base, int64_t n, int pdim, uint32_t chunk,
-                                int nhot = 0, int64_t hot_batch = 0, int64_t hot_bytes = 0,
-                                const EcList* ec = nullptr, int64_t ec_occ = 0,
-                                const EcList* eh = nullptr, int64_t eh_occ = 0) {
+// partial rows of pdim floats, sized for split-mode chunks (kChunk: every mode's chunks are
+// at least that long), the hot-shaped tables of `hot` and the early-chain lists `ec` / `eh`
+// with their occurrences.  Callers go through plan_update / plan_index_ws below.
+inline UpdateWs carve_update_ws(char* base, int64_t n, int pdim, const HotSizes& hot,
+                                const EcList& ec, int64_t ec_occ, const EcList& eh,
+                                int64_t eh_occ) {
+    constexpr uint32_t chunk = kChunk;
     UpdateWs w;
     // every buffer 256-byte aligned whatever the caller's workspace alignment (the
     // 16-byte key / index / LDS-DMA loads rely on it): the layout starts at the first
@@ -2550,8 +2595,8 @@ inline UpdateWs carve_update_ws(char* base, int64_t n, int pdim, uint32_t chunk,
     w.chain_part = (uint32_t*)take(4 * scan_part_entries(mmax + 1));
     w.chain_trec = (ChainTile*)take((int64_t)sizeof(ChainTile) * tmax);
     w.chain_tcnt = (uint32_t*)take(20 * tmax);
-    auto carve_ec = [&](const EcList* l, int64_t occ) {
-        const int64_t recs = l && l->n ? l->cb0[l->n] : 0, M = l && l->n ? l->col0[l->n] : 0;
+    auto carve_ec = [&](const EcList& l, int64_t occ) {
+        const int64_t recs = l.n ? l.cb0[l.n] : 0, M = l.n ? l.col0[l.n] : 0;
         UpdateWs::EcWs e;
         e.stats = (uint32_t*)take(4 * kEcStats * recs);
         e.boff = (uint32_t*)take(4 * recs);
@@ -2567,22 +2612,49 @@ inline UpdateWs carve_update_ws(char* base, int64_t n, int pdim, uint32_t chunk,
     };
     w.ec = carve_ec(ec, ec_occ);
     w.eh = carve_ec(eh, eh_occ);
-    w.eh_cand = (uint32_t*)take(eh && eh->n ? 4 * (int64_t)kEhK * eh->n : 0);
-    w.hot_nw = (int)((hot_batch + kHotWin - 1) / kHotWin);
+    w.eh_cand = (uint32_t*)take(eh.n ? 4 * (int64_t)kEhK * eh.n : 0);
+    w.hot_nw = (int)((hot.batch + kHotWin - 1) / kHotWin);
     w.hot_hist = nullptr;
     w.hot_cnt = nullptr;
     w.hot_key = nullptr;
     w.hot_part = nullptr;
     w.hot_slots = nullptr;
-    if (nhot > 0 && w.hot_nw > 0) {
-        w.hot_slots = (uint8_t*)take(hot_bytes);
+    if (hot.n > 0 && w.hot_nw > 0) {
+        w.hot_slots = (uint8_t*)take(hot.bytes);
         w.hot_hist = (uint32_t*)take(4 * (32 * 32 + 32));
         w.hot_cnt = w.hot_hist ? w.hot_hist + 32 * 32 : nullptr;
         w.hot_key = (uint32_t*)take(4 * 32 * kHotSlots);
-        w.hot_part = (float2*)take((int64_t)nhot * kHotSlots * w.hot_nw * 64 * 8);
+        w.hot_part = (float2*)take((int64_t)hot.n * kHotSlots * w.hot_nw * 64 * 8);
     }
     w.bytes = off;
     return w;
+}
+
+// The workspace of one et_sparse_sgd call and the lists its layout was sized from, which
+// the call needs afterwards: the early-chain tables, the big tables' hot-column list (both
+// whatever the flags: the size cannot depend on them) and the hot-shaped tables.
+struct UpdatePlan {
+    UpdateWs ws;
+    EcList ec, eh;
+    HotSizes hot;
+};
+// The only place that turns descriptors into a layout (base == nullptr: into a size).
+inline UpdatePlan plan_update(const et_update_desc* descs, int ntables, int64_t n, int pdim,
+                              char* base) {
+    UpdatePlan p;
+    p.hot = hot_sizes(descs, ntables);
+    int64_t ec_occ, eh_occ;
+    p.ec = ec_list(descs, ntables, &ec_occ);
+    p.eh = ec_list(descs, ntables, &eh_occ, true);
+    p.ws = carve_update_ws(base, n, pdim, p.hot, p.ec, ec_occ, p.eh, eh_occ);
+    return p;
+}
+
+// The index phase's layout alone — no gradient rows (pdim 0), no hot-shaped table, no early
+// chains — for callers that run group_occurrences over one index vector: the device Indexer
+// and the ragged update, which append their own buffers at `bytes`.
+inline UpdateWs plan_index_ws(char* base, int64_t n) {
+    return carve_update_ws(base, n, 0, HotSizes{}, EcList{}, 0, EcList{}, 0);
 }
 
 // Steps 1-4 shared by et_sparse_sgd: sorted keys/values, segments and chunks.
@@ -2615,7 +2687,7 @@ inline Grouped grouped_pairs(const UpdatePack& pack, int ntables, const UpdateWs
 // stream (forked after the chunk records) while the caller's stream goes on to the chunk pass
 // over the single-chunk columns (k_sgd_exact) — the plan is off the update's critical path.
 inline int launch_chain_plan(const UpdatePack& pack, int ntables, int64_t n, uint32_t sent,
-                             uint32_t chunk, UpdateWs& w, const Grouped& out, hipStream_t s,
+                             uint32_t chunk, const UpdateWs& w, const Grouped& out, hipStream_t s,
                              uint32_t ec_mask, const EhMap& eh, hipEvent_t cand_ready) {
     if (eh.mask) ET_HIP_CHECK(hipStreamWaitEvent(s, cand_ready, 0));  // k_eh_pick's candidates
     const int64_t mmax = n / chunk + 2;
@@ -2650,20 +2722,21 @@ inline int launch_chain_plan(const UpdatePack& pack, int ntables, int64_t n, uin
                        w.chain_trec, w.chain_tcnt, w.chain_cnt, w.chain_info, w.chain_e0,
                        w.chain_ent, w.chains);
     ET_LAUNCH_CHECK("k_chain_emit");
-    // ET_CHAIN_CHECK (experiment builds): validate every entry of the plan
+#ifdef ET_EXPERIMENTS
+    // ET_CHAIN_CHECK=1: validate every entry of the plan
     if (ET_KNOB("ET_CHAIN_CHECK", 0))
         hipLaunchKernelGGL(k_chain_check, dim3(cg), dim3(256), 0, s, pack, ntables, w.counters,
                            w.chain_cnt, w.chain_info, w.chain_ent, w.chains, w.chain_order);
+#endif
     return ET_OK;
 }
 
+// Steps 1-4: the sorted pairs (`out`), segments, chunks and chunk records of n occurrences
+// in the workspace; with a hot mask and list, the hot columns picked and retired too.
 inline int group_occurrences(const UpdatePack& pack, int ntables, int64_t n, uint32_t sent,
-                             uint32_t chunk, UpdateWs& w, Grouped& out, hipStream_t s,
+                             uint32_t chunk, const UpdateWs& w, Grouped& out, hipStream_t s,
                              uint32_t hot_mask = 0, const HotList* hl = nullptr,
-                             bool chain = false, uint32_t ec_mask = 0,
                              int64_t* const* snaps = nullptr) {
-    const int64_t blocks = cdiv64(n, 256);
-    const unsigned kb_grid = (unsigned)(blocks < 65536 ? blocks : 65536);
     ET_HIP_CHECK(hipMemsetAsync(w.counters, 0, 4 * kCntSlots, s));
     KeyGrid kg;
     kg.blk_off[0] = 0;
@@ -2686,7 +2759,6 @@ inline int group_occurrences(const UpdatePack& pack, int ntables, int64_t n, uin
         nb = nb < 2048 ? nb : 2048;  // grid-stride beyond 2048 workgroups per table
         kg.blk_off[t + 1] = kg.blk_off[t] + (uint32_t)nb;
     }
-    (void)kb_grid;
     RsSegment seg[ET_MAX_TABLES_PER_LAUNCH];
     const int P = sort_segments(pack, ntables, seg);
     kg.in_b = 0;
@@ -2743,7 +2815,8 @@ inline int group_occurrences(const UpdatePack& pack, int ntables, int64_t n, uin
 }
 
 // Float32 tables on the vector kernels, grouped by power-of-two capacity (one pass of
-// k_sgd_chunks / k_sgd_combine per capacity; each pass skips the other tables).
+// k_sgd_chunks5 / k_sgd_tail, or of k_sgd_exact, per capacity; each pass skips the other
+// tables).
 struct VecGroups {
     int n = 0;
     int cap[8];
@@ -2761,10 +2834,16 @@ struct VecGroups {
     }
 };
 
-// Single-occurrence columns through k_sgd_singles (ET_SGD_SINGLES=0 in an experiment build
-// turns it off) and the chunk pass at 5 waves per SIMD (ET_SGD_OCC5=0: k_sgd_chunks).
-inline bool sgd_singles() { return ET_KNOB("ET_SGD_SINGLES", 1) != 0; }
-inline bool sgd_chunks_occ5() { return ET_KNOB("ET_SGD_OCC5", 1) != 0; }
+// f(std::integral_constant<int, D>{}) for the row capacity D == cap of a VecGroups entry
+// (16 .. 2048; any other value calls nothing).
+template <int... Ds, typename F>
+void with_capacity_in(int cap, F&& f) {
+    ((cap == Ds ? f(std::integral_constant<int, Ds>{}) : void()), ...);
+}
+template <typename F>
+void with_capacity(int cap, F&& f) {
+    with_capacity_in<16, 32, 64, 128, 256, 512, 1024, 2048>(cap, f);
+}
 
 // The chains of an exact update phase: the side streams of the early chains and of the early
 // hot columns (null: none) and their column counts, the side stream of the regular chains
@@ -2775,6 +2854,29 @@ struct ChainRun {
     hipStream_t eh_side = nullptr;  // the early hot columns (EH)
     uint32_t eh_ncols = 0;
     hipStream_t side = nullptr;
+};
+
+// One update phase, filled once by et_sparse_sgd and handed down by const reference to
+// every host launcher (never to a kernel: their argument lists are their own).  The
+// learning rate in the accumulator type travels beside it, typed by the variant.
+struct SgdRun {
+    UpdatePack pack;
+    int ntables = 0;
+    int64_t n = 0;       // occurrences of all tables
+    int pdim = 0;        // widest dim, rounded up to 4: floats per partial row
+    uint32_t chunk = 0;  // occurrences per chunk in this call's mode
+    uint32_t sent = 0;   // key of out-of-range occurrences (sorts last)
+    double eta64 = 0.0;
+    Grouped gr = {};
+    UpdateWs w = {};
+    VecGroups vg;
+    bool any_generic = false;  // some table takes the generic kernels
+    HotList hl = {};
+    unsigned grid = 0;   // sgd_grid(n)
+    bool chain = false;  // exact mode with serial chains
+    ChainRun cr;
+    hipStream_t s = nullptr;  // the caller's stream
+    int slices() const { return (pdim + 63) / 64; }  // 64-feature slices of a chain column
 };
 
 // Chain workgroups (one CU each): 32 early, 32 early-hot, 128 regular, so the regular chains
@@ -2789,6 +2891,7 @@ constexpr unsigned kEcWg = 32, kEhWg = 32, kRegWg = 128;
 // early hot columns 4.10-4.34 ms, profiles/r04/ab_exact_grid.txt): the regular chains run
 // beside the chunk pass, which needs those SIMDs more.
 constexpr unsigned kChainExcl = 5;
+
 // The exact mode's chunk pass + singles run at most 512 + 512 grid-stride workgroups: fewer in
 // flight than the split mode's 16384 + 16384 leaves the fabric to the latency-bound chains
 // beside it (config 4, A/B twice on one box: 4.22-4.24 ms at the split mode's grid, 4.05-4.06
@@ -2800,11 +2903,25 @@ constexpr unsigned kChainExcl = 5;
 // 4.16 at 512, profiles/r05/exact_grid/).
 constexpr unsigned kExactGrid = 384;
 
-// k_sgd_chains on stream `s`: zero the item counter, at most `nb` workgroups.
+// A planned chain list: which one it is (the kernels' `list` argument, for timelines; bit
+// (int)id of kChainExcl says whether it runs on SIMDs of its own), where its plan lies in the
+// workspace and the side stream it runs on.
+enum class ChainListId : uint32_t { kEarly = 0, kRegular = 1, kEarlyHot = 2 };
+struct ChainList {
+    ChainListId id;
+    uint32_t* counters;
+    const ChainCol* chains;
+    const uint32_t* order;
+    ChainEnt ent;
+    hipStream_t side;
+};
+
+// One chain list on its side stream: zero its item counter, then at most `nb` workgroups of
+// k_sgd_chains, or of k_sgd_chains_x for a list on SIMDs of its own.
 template <typename T, typename C, int MODE, bool NT>
-int launch_chains(const UpdatePack& pack, int ntables, uint32_t* counters, const ChainCol* chains,
-                  const uint32_t* order, const ChainEnt& ce, int ns, C eta_c, double eta64,
-                  unsigned nb, hipStream_t s, bool excl, uint32_t list, bool wide = false) {
+int launch_chains(const SgdRun& r, C eta_c, const ChainList& l, int64_t nb) {
+    const bool excl = (((unsigned)ET_KNOB("ET_CHAIN_EXCL", kChainExcl) >> (uint32_t)l.id) & 1u) != 0;
+    uint32_t list = (uint32_t)l.id;
     if (ET_KNOB("ET_CHAIN_STREAM", 1)) list |= 0x100u;
     // the quad walk for Float32 S = 1 chains of at least this many 64-entry groups (§9 "The
     // quad walk": every S = 1 chain 5.56 ms, >= 4 K / 16 K / 64 K / 128 K entries 5.20 / 4.99 /
@@ -2818,63 +2935,47 @@ int launch_chains(const UpdatePack& pack, int ntables, uint32_t* counters, const
         reinterpret_cast<const void*>(&k_sgd_chains_x<T, C, MODE, NT>),
         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kChainReserveLds);
     ET_HIP_CHECK(attr_x);
-    static const hipError_t attr_w = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&k_sgd_chains_w<T, C, MODE, NT>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)kChainReserveLds);
-    ET_HIP_CHECK(attr_w);
-    ET_HIP_CHECK(hipMemsetAsync(counters + kCntNext, 0, 4, s));
-    if (wide) {
-        hipLaunchKernelGGL((k_sgd_chains_w<T, C, MODE, NT>), dim3(nb), dim3(512),
-                           kChainReserveLds, s, pack, ntables, counters, chains, order, ce, ns,
-                           eta_c, eta64, quad_min, list);
-        ET_LAUNCH_CHECK("k_sgd_chains_w");
-        return ET_OK;
-    }
+    ET_HIP_CHECK(hipMemsetAsync(l.counters + kCntNext, 0, 4, l.side));
     if (excl) {
-        hipLaunchKernelGGL((k_sgd_chains_x<T, C, MODE, NT>), dim3(nb), dim3(256),
-                           kChainReserveLds, s, pack, ntables, counters, chains, order, ce, ns,
-                           eta_c, eta64, quad_min, list);
+        hipLaunchKernelGGL((k_sgd_chains_x<T, C, MODE, NT>), dim3((unsigned)nb), dim3(256),
+                           kChainReserveLds, l.side, r.pack, r.ntables, l.counters, l.chains,
+                           l.order, l.ent, r.slices(), eta_c, r.eta64, quad_min, list);
         ET_LAUNCH_CHECK("k_sgd_chains_x");
         return ET_OK;
     }
-    hipLaunchKernelGGL((k_sgd_chains<T, C, MODE, NT>), dim3(nb), dim3(256), kChainReserveLds, s,
-                       pack, ntables, counters, chains, order, ce, ns, eta_c, eta64, quad_min,
-                       list);
+    hipLaunchKernelGGL((k_sgd_chains<T, C, MODE, NT>), dim3((unsigned)nb), dim3(256),
+                       kChainReserveLds, l.side, r.pack, r.ntables, l.counters, l.chains, l.order,
+                       l.ent, r.slices(), eta_c, r.eta64, quad_min, list);
     ET_LAUNCH_CHECK("k_sgd_chains");
     return ET_OK;
 }
 
 // The three chain lists of an exact update phase on their side streams: the early chains and
-// the early hot columns (already planned) and the regular chains.
+// the early hot columns (already planned; one workgroup per four (column, slice) items, at
+// most kEcWg / kEhWg) and the regular chains.
 template <typename T, typename C, int MODE, bool NT>
-int launch_chain_lists(const UpdatePack& pack, int ntables, UpdateWs& w, int ns, C eta_c,
-                       double eta64, const ChainRun& cr) {
-    const unsigned excl = (unsigned)ET_KNOB("ET_CHAIN_EXCL", kChainExcl);
-    int rc;
+int launch_chain_lists(const SgdRun& r, C eta_c) {
+    const UpdateWs& w = r.w;
+    const ChainRun& cr = r.cr;
     if (cr.ec_side) {
-        const int64_t items = (int64_t)cr.ec_ncols * ns;
-        const unsigned wg = (unsigned)ET_KNOB("ET_EC_WG", kEcWg);
-        const unsigned eb = (unsigned)(cdiv64(items, 4) < wg ? cdiv64(items, 4) : wg);
-        rc = launch_chains<T, C, MODE, NT>(pack, ntables, w.ec.counters, w.ec.chains, w.ec.order,
-                                           w.ec.ent, ns, eta_c, eta64, eb, cr.ec_side,
-                                           (excl & 1u) != 0, 0u);
+        const ChainList l{ChainListId::kEarly, w.ec.counters, w.ec.chains, w.ec.order, w.ec.ent,
+                          cr.ec_side};
+        const int64_t wg = ET_KNOB("ET_EC_WG", (long long)kEcWg);
+        const int rc = launch_chains<T, C, MODE, NT>(
+            r, eta_c, l, std::min(cdiv64((int64_t)cr.ec_ncols * r.slices(), 4), wg));
         if (rc != ET_OK) return rc;
     }
     if (cr.eh_side) {
-        const int64_t items = (int64_t)cr.eh_ncols * ns;
-        const unsigned wg = (unsigned)ET_KNOB("ET_EH_WG", kEhWg);
-        const unsigned eb = (unsigned)(cdiv64(items, 4) < wg ? cdiv64(items, 4) : wg);
-        // ET_EH_WIDE (experiments): eight waves per early-hot workgroup (k_sgd_chains_w)
-        const bool wide = ET_KNOB("ET_EH_WIDE", 0) != 0;
-        rc = launch_chains<T, C, MODE, NT>(pack, ntables, w.eh.counters, w.eh.chains, w.eh.order,
-                                           w.eh.ent, ns, eta_c, eta64, eb, cr.eh_side,
-                                           (excl & 4u) != 0 && !wide, 2u, wide);
+        const ChainList l{ChainListId::kEarlyHot, w.eh.counters, w.eh.chains, w.eh.order, w.eh.ent,
+                          cr.eh_side};
+        const int64_t wg = ET_KNOB("ET_EH_WG", (long long)kEhWg);
+        const int rc = launch_chains<T, C, MODE, NT>(
+            r, eta_c, l, std::min(cdiv64((int64_t)cr.eh_ncols * r.slices(), 4), wg));
         if (rc != ET_OK) return rc;
     }
-    return launch_chains<T, C, MODE, NT>(pack, ntables, w.counters, w.chains, w.chain_order,
-                                         w.chain_ent, ns, eta_c, eta64,
-                                         (unsigned)ET_KNOB("ET_CHAIN_WG", kRegWg), cr.side,
-                                         (excl & 2u) != 0, 1u);
+    const ChainList l{ChainListId::kRegular, w.counters, w.chains, w.chain_order, w.chain_ent,
+                      cr.side};
+    return launch_chains<T, C, MODE, NT>(r, eta_c, l, ET_KNOB("ET_CHAIN_WG", (long long)kRegWg));
 }
 
 // The update phase of an exact Float32 call: the chain lists on the side streams, the chunk
@@ -2882,39 +2983,23 @@ int launch_chain_lists(const UpdatePack& pack, int ntables, UpdateWs& w, int ns,
 // caller's stream, then the generic tables' single-chunk columns.  No partial sums, no
 // combine.
 template <int MODE, bool NT>
-int launch_sgd_exact(const UpdatePack& pack, int ntables, const Grouped& gr, UpdateWs& w,
-                     int pdim, uint32_t sent, float eta32, double eta64, const VecGroups& vg,
-                     bool any_generic, hipStream_t s, unsigned grid, const ChainRun& cr) {
-    const int ns = (pdim + 63) / 64;
+int launch_sgd_exact(const SgdRun& r, float eta32) {
+    const UpdateWs& w = r.w;
     const unsigned xcap = (unsigned)ET_KNOB("ET_EXACT_GRID", kExactGrid);
-    grid = grid < xcap ? grid : xcap;
-    int rc = launch_chain_lists<float, float, MODE, NT>(pack, ntables, w, ns, eta32, eta64, cr);
+    const unsigned grid = r.grid < xcap ? r.grid : xcap;
+    int rc = launch_chain_lists<float, float, MODE, NT>(r, eta32);
     if (rc != ET_OK) return rc;
-#define ET_SGD_EXACT(DD)                                                                       \
-    case DD:                                                                                   \
-        hipLaunchKernelGGL((k_sgd_exact<DD, MODE, NT>), dim3(2 * grid), dim3(256), 0, s, pack, \
-                           ntables, gr.keys, gr.vals, w.recs, w.counters, sent, eta32, eta64,  \
-                           vg.mask[i], grid);                                                  \
-        break;
-    for (int i = 0; i < vg.n; ++i) {
-        switch (vg.cap[i]) {
-            ET_SGD_EXACT(16)
-            ET_SGD_EXACT(32)
-            ET_SGD_EXACT(64)
-            ET_SGD_EXACT(128)
-            ET_SGD_EXACT(256)
-            ET_SGD_EXACT(512)
-            ET_SGD_EXACT(1024)
-            ET_SGD_EXACT(2048)
-            default: break;
-        }
-    }
-#undef ET_SGD_EXACT
+    for (int i = 0; i < r.vg.n; ++i)
+        with_capacity(r.vg.cap[i], [&](auto cap) {
+            hipLaunchKernelGGL((k_sgd_exact<decltype(cap)::value, MODE, NT>), dim3(2 * grid),
+                               dim3(256), 0, r.s, r.pack, r.ntables, r.gr.keys, r.gr.vals, w.recs,
+                               w.counters, r.sent, eta32, r.eta64, r.vg.mask[i], grid);
+        });
     ET_LAUNCH_CHECK("k_sgd_exact");
-    if (any_generic) {
+    if (r.any_generic) {
         hipLaunchKernelGGL((k_sgd_chunks_generic<float, float, MODE, NT>), dim3(grid), dim3(256),
-                           0, s, pack, ntables, gr.keys, gr.vals, w.recs, w.counters, w.partials,
-                           pdim, sent, eta32, eta64, 1);
+                           0, r.s, r.pack, r.ntables, r.gr.keys, r.gr.vals, w.recs, w.counters,
+                           w.partials, r.pdim, r.sent, eta32, r.eta64, 1);
         ET_LAUNCH_CHECK("k_sgd_chunks_generic");
     }
     return ET_OK;
@@ -2924,90 +3009,65 @@ int launch_sgd_exact(const UpdatePack& pack, int ntables, const Grouped& gr, Upd
 // (walked by chain_walk_wide in the accumulator type) beside the generic chunk pass over the
 // single-chunk columns (one wave per chunk, serial in occurrence order).
 template <typename T, typename C, int MODE, bool NT>
-int launch_sgd_exact_generic(const UpdatePack& pack, int ntables, const Grouped& gr, UpdateWs& w,
-                             int pdim, uint32_t sent, C eta_c, double eta64, hipStream_t s,
-                             unsigned grid, const ChainRun& cr) {
-    int rc = launch_chain_lists<T, C, MODE, NT>(pack, ntables, w, (pdim + 63) / 64, eta_c, eta64,
-                                                cr);
+int launch_sgd_exact_generic(const SgdRun& r, C eta_c) {
+    const UpdateWs& w = r.w;
+    int rc = launch_chain_lists<T, C, MODE, NT>(r, eta_c);
     if (rc != ET_OK) return rc;
-    hipLaunchKernelGGL((k_sgd_chunks_generic<T, C, MODE, NT>), dim3(grid), dim3(256), 0, s, pack,
-                       ntables, gr.keys, gr.vals, w.recs, w.counters,
-                       reinterpret_cast<C*>(w.partials), pdim, sent, eta_c, eta64, 1);
+    hipLaunchKernelGGL((k_sgd_chunks_generic<T, C, MODE, NT>), dim3(r.grid), dim3(256), 0, r.s,
+                       r.pack, r.ntables, r.gr.keys, r.gr.vals, w.recs, w.counters,
+                       reinterpret_cast<C*>(w.partials), r.pdim, r.sent, eta_c, r.eta64, 1);
     ET_LAUNCH_CHECK("k_sgd_chunks_generic");
     return ET_OK;
 }
 
+// The update phase of one variant: the exact mode's launchers above when the call has
+// chains, else the split-mode passes (steps 5h-7 of the pipeline at the top of this file).
 template <typename T, typename C, int MODE, bool NT>
-int launch_sgd_typed(const UpdatePack& pack, int ntables, const Grouped& gr, UpdateWs& w,
-                     uint32_t chunk, int pdim, uint32_t sent, C eta_c, double eta64,
-                     const VecGroups& vg, bool any_generic, hipStream_t s,
-                     const HotList& hl, unsigned grid, bool chain, const ChainRun& cr) {
-    if (chain) {
+int launch_sgd_typed(const SgdRun& r, C eta_c) {
+    const UpdateWs& w = r.w;
+    const unsigned grid = r.grid;
+    hipStream_t s = r.s;
+    if (r.chain) {
         if constexpr (__is_same(T, float))
-            return launch_sgd_exact<MODE, NT>(pack, ntables, gr, w, pdim, sent, eta_c, eta64, vg,
-                                              any_generic, s, grid, cr);
+            return launch_sgd_exact<MODE, NT>(r, eta_c);
         else
-            return launch_sgd_exact_generic<T, C, MODE, NT>(pack, ntables, gr, w, pdim, sent,
-                                                            eta_c, eta64, s, grid, cr);
+            return launch_sgd_exact_generic<T, C, MODE, NT>(r, eta_c);
     }
     if constexpr (__is_same(T, float)) {
-        const bool singles = sgd_singles();
         // combine workgroups of k_sgd_tail: a quarter of one resident wave of workgroups,
         // so the singles start at once beside them
         const unsigned ncomb = grid < 256u ? grid : 256u;
-        if (hl.n > 0 && w.hot_part) {
-            hipLaunchKernelGGL(k_sgd_hot, dim3((unsigned)w.hot_nw, (unsigned)hl.n), dim3(256), 0, s,
-                               pack, hl, w.hot_cnt, w.hot_slots, w.hot_part, w.hot_nw);
+        if (r.hl.n > 0 && w.hot_part) {
+            hipLaunchKernelGGL(k_sgd_hot, dim3((unsigned)w.hot_nw, (unsigned)r.hl.n), dim3(256), 0,
+                               s, r.pack, r.hl, w.hot_cnt, w.hot_slots, w.hot_part, w.hot_nw);
             hipLaunchKernelGGL((k_hot_combine<MODE, NT>),
-                               dim3((unsigned)cdiv64((int64_t)hl.n * kHotSlots, 4)), dim3(256), 0,
-                               s, pack, hl, w.hot_cnt, w.hot_key, w.hot_part, w.hot_nw,
-                               (float)eta_c, eta64);
+                               dim3((unsigned)cdiv64((int64_t)r.hl.n * kHotSlots, 4)), dim3(256), 0,
+                               s, r.pack, r.hl, w.hot_cnt, w.hot_key, w.hot_part, w.hot_nw,
+                               (float)eta_c, r.eta64);
             ET_LAUNCH_CHECK("k_sgd_hot");
         }
-#define ET_SGD_VEC(DD)                                                                         \
-    case DD:                                                                                   \
-        if (sgd_chunks_occ5())                                                                 \
-            hipLaunchKernelGGL((k_sgd_chunks5<DD, MODE, NT>), dim3(grid), dim3(256), 0, s,     \
-                               pack, ntables, gr.keys, gr.vals, w.recs, w.counters,            \
-                               w.partials, pdim, sent, eta_c, eta64, vg.mask[i],               \
-                               singles ? 1 : 0);                                               \
-        else                                                                                   \
-            hipLaunchKernelGGL((k_sgd_chunks<DD, MODE, NT>), dim3(grid), dim3(256), 0, s,      \
-                               pack, ntables, gr.keys, gr.vals, w.recs, w.counters,            \
-                               w.partials, pdim, sent, eta_c, eta64, vg.mask[i],               \
-                               singles ? 1 : 0);                                               \
-        if (singles)                                                                           \
-            hipLaunchKernelGGL((k_sgd_tail<DD, MODE, NT>), dim3(grid + ncomb), dim3(256), 0, s, \
-                               pack, ntables, gr.keys, gr.vals, w.recs, w.seg_start, w.multi,  \
-                               w.counters, w.mlist, w.partials, pdim, sent, eta_c, eta64,      \
-                               vg.mask[i], ncomb);                                             \
-        else                                                                                   \
-            hipLaunchKernelGGL((k_sgd_combine<DD, MODE, NT>), dim3(grid), dim3(256), 0, s,     \
-                               pack, ntables, gr.keys, w.seg_start, w.multi, w.counters,       \
-                               w.mlist, w.partials, pdim, sent, eta_c, eta64, vg.mask[i]);     \
-        break;
-        for (int i = 0; i < vg.n; ++i) switch (vg.cap[i]) {
-            ET_SGD_VEC(16)
-            ET_SGD_VEC(32)
-            ET_SGD_VEC(64)
-            ET_SGD_VEC(128)
-            ET_SGD_VEC(256)
-            ET_SGD_VEC(512)
-            ET_SGD_VEC(1024)
-            ET_SGD_VEC(2048)
-            default: break;
-            }
-#undef ET_SGD_VEC
-        ET_LAUNCH_CHECK("k_sgd_chunks");
+        // the chunk pass leaves the single-occurrence columns (skip_singles = 1) to the tail
+        for (int i = 0; i < r.vg.n; ++i)
+            with_capacity(r.vg.cap[i], [&](auto cap) {
+                constexpr int D = decltype(cap)::value;
+                hipLaunchKernelGGL((k_sgd_chunks5<D, MODE, NT>), dim3(grid), dim3(256), 0, s,
+                                   r.pack, r.ntables, r.gr.keys, r.gr.vals, w.recs, w.counters,
+                                   w.partials, r.pdim, r.sent, eta_c, r.eta64, r.vg.mask[i], 1);
+                hipLaunchKernelGGL((k_sgd_tail<D, MODE, NT>), dim3(grid + ncomb), dim3(256), 0, s,
+                                   r.pack, r.ntables, r.gr.keys, r.gr.vals, w.recs, w.seg_start,
+                                   w.multi, w.counters, w.mlist, w.partials, r.pdim, r.sent, eta_c,
+                                   r.eta64, r.vg.mask[i], ncomb);
+            });
+        ET_LAUNCH_CHECK("k_sgd_chunks5");
     }
-    if (any_generic) {
+    if (r.any_generic) {
         C* partials = reinterpret_cast<C*>(w.partials);
         hipLaunchKernelGGL((k_sgd_chunks_generic<T, C, MODE, NT>), dim3(grid), dim3(256), 0, s,
-                           pack, ntables, gr.keys, gr.vals, w.recs, w.counters, partials, pdim,
-                           sent, eta_c, eta64, 0);
+                           r.pack, r.ntables, r.gr.keys, r.gr.vals, w.recs, w.counters, partials,
+                           r.pdim, r.sent, eta_c, r.eta64, 0);
         hipLaunchKernelGGL((k_sgd_combine_generic<T, C, MODE, NT>), dim3(grid), dim3(256), 0, s,
-                           pack, ntables, gr.keys, w.seg_start, w.multi, w.counters, partials,
-                           pdim, sent, eta_c, eta64);
+                           r.pack, r.ntables, r.gr.keys, w.seg_start, w.multi, w.counters, partials,
+                           r.pdim, r.sent, eta_c, r.eta64);
         ET_LAUNCH_CHECK("k_sgd_chunks_generic");
     }
     return ET_OK;
@@ -3030,25 +3090,38 @@ inline double convert_eta(int dtype, double eta) {
     }
 }
 
-// Element type + accumulator dispatch, then MODE / NT.
+// The kernel variant of an update call (et_sparse_sgd, et_update_indexed, et_ragged_sgd)
+// from its element type and flags: f(Elem<T, C>{}, Mode<MODE>{}, std::bool_constant<NT>{}),
+// T the table and gradient type, C the accumulator (sgd_apply_t), MODE 0 fused, 1 unfused,
+// 2 unfused with a Float64 learning rate, NT non-temporal stores.  `dtype` is one of the
+// four float types (checked by the caller, which names itself in the message).
 template <typename T, typename C>
-int launch_sgd_dtype(const UpdatePack& pack, int ntables, const Grouped& gr, UpdateWs& w,
-                     uint32_t chunk, int pdim, uint32_t sent, double eta_c, double eta64,
-                     int mode, bool nt, const VecGroups& vg, bool any_generic, hipStream_t s,
-                     const HotList& hl, unsigned grid, bool chain, const ChainRun& cr) {
-#define ET_SGD_CALL(M, NTV)                                                                \
-    return launch_sgd_typed<T, C, M, NTV>(pack, ntables, gr, w, chunk, pdim, sent, (C)eta_c, \
-                                          eta64, vg, any_generic, s, hl, grid, chain, cr)
-    if (mode == 0) {
-        if (nt) ET_SGD_CALL(0, true);
-        ET_SGD_CALL(0, false);
-    } else if (mode == 1) {
-        if (nt) ET_SGD_CALL(1, true);
-        ET_SGD_CALL(1, false);
+struct Elem {
+    using type = T;
+    using acc = C;
+};
+template <int M>
+using Mode = std::integral_constant<int, M>;
+
+template <typename F>
+int dispatch_sgd(int dtype, uint32_t flags, F&& f) {
+    const bool nt = (flags & ET_FLAG_NONTEMPORAL) != 0;
+    const int mode = (flags & ET_FLAG_SGD_UNFUSED) ? ((flags & ET_FLAG_SGD_F64_ALPHA) ? 2 : 1) : 0;
+    auto with_elem = [&](auto e) -> int {
+        auto with_mode = [&](auto m) -> int {
+            return nt ? f(e, m, std::true_type{}) : f(e, m, std::false_type{});
+        };
+        return mode == 0 ? with_mode(Mode<0>{}) : mode == 1 ? with_mode(Mode<1>{})
+                                                            : with_mode(Mode<2>{});
+    };
+    switch (dtype) {
+        case ET_F32: return with_elem(Elem<float, float>{});
+        case ET_F64: return with_elem(Elem<double, double>{});
+        case ET_BF16: return with_elem(Elem<__bf16, float>{});
+        default:  // ET_F16
+            if (flags & ET_FLAG_F16_FP32_ACC) return with_elem(Elem<_Float16, float>{});
+            return with_elem(Elem<_Float16, _Float16>{});
     }
-    if (nt) ET_SGD_CALL(2, true);
-    ET_SGD_CALL(2, false);
-#undef ET_SGD_CALL
 }
 
 // Workgroups of the chunk / combine passes (grid-stride): one per 2048 occurrences,
@@ -3057,26 +3130,6 @@ int launch_sgd_dtype(const UpdatePack& pack, int ntables, const Grouped& gr, Upd
 inline unsigned sgd_grid(int64_t n) {
     const int64_t g = cdiv64(n, 2048);
     return (unsigned)(g < 256 ? 256 : g > 16384 ? 16384 : g);
-}
-
-// Tables the hot-column pass can take (the workspace is sized for all of them).
-inline bool hot_shape(const et_update_desc& d) {
-    return d.dim == 128 && d.pool >= 1 && d.pool <= kHotMaxPool && d.batch > 0;
-}
-
-// Hot-shaped tables: their count, largest batch, and slot-byte offsets (soff[t]) / total.
-inline void hot_sizes(const et_update_desc* descs, int ntables, int* nhot, int64_t* batch,
-                      int64_t* bytes, uint64_t* soff = nullptr) {
-    *nhot = 0;
-    *batch = 0;
-    *bytes = 0;
-    for (int t = 0; t < ntables; ++t)
-        if (hot_shape(descs[t])) {
-            ++*nhot;
-            if (descs[t].batch > *batch) *batch = descs[t].batch;
-            if (soff) soff[t] = (uint64_t)*bytes;
-            *bytes += descs[t].batch * ((descs[t].pool + 3) & ~3);
-        }
 }
 
 inline int validate_update(const et_update_desc* descs, int ntables, int64_t* n_out,
@@ -3111,41 +3164,6 @@ inline int validate_update(const et_update_desc* descs, int ntables, int64_t* n_
     return ET_OK;
 }
 
-// Early-chain tables of these descriptors (ec_table) and their occurrences; the list
-// sizes the workspace whatever the flags, and et_sparse_sgd uses it in exact Float32 mode.
-// hot = true: the big tables' hot-column list (eh_table, kEhK slots each; empty unless ET_EH).
-inline EcList ec_list(const et_update_desc* descs, int ntables, int64_t* occ, bool hot = false) {
-    EcList ec;
-    ec.n = 0;
-    ec.mask = 0;
-    ec.hot = hot ? 1 : 0;
-    ec.blk0[0] = ec.col0[0] = ec.cb0[0] = 0;
-    *occ = 0;
-    if (hot && !eh_enabled()) return ec;
-    for (int t = 0; t < ntables; ++t) {
-        const et_update_desc& d = descs[t];
-        if (hot ? !eh_table(d) : !ec_table(d)) continue;
-        const uint32_t nb = (uint32_t)cdiv64(d.batch, kEcBags);
-        const uint32_t cols = hot ? (uint32_t)kEhK : (uint32_t)d.nrows;
-        ec.t[ec.n] = t;
-        ec.mask |= 1u << t;
-        ec.blk0[ec.n + 1] = ec.blk0[ec.n] + nb;
-        ec.col0[ec.n + 1] = ec.col0[ec.n] + cols;
-        ec.cb0[ec.n + 1] = ec.cb0[ec.n] + nb * cols;
-        *occ += d.pool * d.batch;
-        ++ec.n;
-    }
-    return ec;
-}
-
-inline EhMap eh_map(const EcList& eh) {
-    EhMap m;
-    m.mask = eh.hot ? eh.mask : 0u;
-    for (int t = 0; t < ET_MAX_TABLES_PER_LAUNCH; ++t) m.e[t] = 0;
-    for (int e = 0; e < eh.n && eh.hot; ++e) m.e[eh.t[e]] = (int8_t)e;
-    return m;
-}
-
 // Exact mode: columns of more occurrences than this are serial chains (k_sgd_chains), the
 // rest single chunks of the chunk pass.
 constexpr uint32_t kExactChunk = ET_SGD_CHUNK;
@@ -3171,8 +3189,8 @@ constexpr uint32_t kExactChunk = ET_SGD_CHUNK;
 // update took 5.1-5.3 ms instead of 4.03-4.07 (profiles/r05/capture/).  Moving all of the
 // call's work to library streams (the caller's queue then holds only the join barriers) was
 // tried: 4.15-4.29 ms with other queues open, 4.63-4.69 ms without (the work queue then
-// shares the caller's pipe and its blocked join barrier; ET_WORK_STREAM=1 in experiment
-// builds, profiles/r05/queue_layout.txt).  So the caller's stream keeps the work, and the
+// shares the caller's pipe and its blocked join barrier; a fourth library stream, since
+// removed, profiles/r05/queue_layout.txt).  So the caller's stream keeps the work, and the
 // side queues are opened at the FIRST call into the library on the device, of any entry
 // point (et::open_side_streams(), from every stream-taking ABI function), right after the
 // caller's own queue, before most programs open other streams; init() touches each with an
@@ -3189,17 +3207,14 @@ constexpr uint32_t kExactChunk = ET_SGD_CHUNK;
 // order).  Kept: the side streams at the least priority (below), which leaves the caller's
 // normal-priority queues to the caller and makes a shared pipe cost +16% instead of +30%.
 struct SideStreams {
-    static constexpr int kN = 4;  // early chains, regular chains, early hot columns, work
-    static constexpr int kEc = 0, kReg = 1, kEh = 2, kWork = 3;
+    static constexpr int kN = 3;  // early chains, regular chains, early hot columns
+    static constexpr int kEc = 0, kReg = 1, kEh = 2;
     std::mutex mu;
-    hipStream_t st[kN] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t fork[kN] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t join[kN] = {nullptr, nullptr, nullptr, nullptr};
+    hipStream_t st[kN] = {};
+    hipEvent_t fork[kN] = {};
+    hipEvent_t join[kN] = {};
     hipEvent_t cand = nullptr;  // the hot-column candidates are picked (k_eh_pick)
 };
-
-// The work stream (kWork) exists only for the ET_WORK_STREAM experiment.
-inline int side_stream_count() { return ET_KNOB("ET_WORK_STREAM", 0) ? 4 : 3; }
 
 inline SideStreams* side_streams() {
     static SideStreams streams[64];
@@ -3211,14 +3226,14 @@ inline SideStreams* side_streams() {
     if (!ss.cand) {
         int least = 0, greatest = 0;
         if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return nullptr;
-        const int n = side_stream_count();
+        constexpr int n = SideStreams::kN;
         // The side streams take the LEAST priority (round 6): their queues then come from the
         // low-priority pool, not from the caller's normal-priority queues, and when one does
         // share the caller's pipe the pipe favours the caller's dispatches — config 4 with
         // one or two streams opened before the library's first call: 4.28-4.46 ms instead of
         // 4.72-4.81 at the greatest priority; 3.66-3.71 ms in every other layout measured
-        // (profiles/r06/queue_layout/).  ET_SIDE_HIGH=1 (experiment builds): the greatest.
-        const int prio = ET_KNOB("ET_SIDE_HIGH", 0) ? greatest : least;
+        // (profiles/r06/queue_layout/).
+        const int prio = least;
         for (int i = 0; i < n; ++i)
             if ((!ss.fork[i] && hipEventCreateWithFlags(&ss.fork[i], hipEventDisableTiming)) ||
                 (!ss.join[i] && hipEventCreateWithFlags(&ss.join[i], hipEventDisableTiming)) ||
@@ -3234,21 +3249,21 @@ inline SideStreams* side_streams() {
     return &ss;
 }
 
-// fork(i, from): side stream i waits for everything `from` (default: the caller's stream)
-// has queued so far; the destructor joins every forked side stream into the caller's stream
+// fork(i): side stream i waits for everything the caller's stream has queued so far; the
+// destructor joins every forked side stream into the caller's stream
 // (every return path of et_sparse_sgd).
 struct SideFork {
     SideStreams* ss = nullptr;
     hipStream_t main = nullptr;
     std::unique_lock<std::mutex> lk;
-    bool forked[SideStreams::kN] = {false, false, false, false};
+    bool forked[SideStreams::kN] = {};
     SideFork(SideStreams* s, hipStream_t m) : ss(s), main(m) {
         if (ss) lk = std::unique_lock<std::mutex>(ss->mu);
     }
-    hipStream_t fork(int i, hipStream_t from = nullptr) {
+    hipStream_t fork(int i) {
         if (!ss) return nullptr;
         if (!forked[i]) {
-            if (hipEventRecord(ss->fork[i], from ? from : main) != hipSuccess ||
+            if (hipEventRecord(ss->fork[i], main) != hipSuccess ||
                 hipStreamWaitEvent(ss->st[i], ss->fork[i], 0) != hipSuccess)
                 return nullptr;
             forked[i] = true;
@@ -3318,14 +3333,7 @@ extern "C" int et_sgd_workspace_size(const et_update_desc* descs, int32_t ntable
     int pdim;
     int rc = et::validate_update(descs, ntables, &n, &rows, &pdim);
     if (rc != ET_OK) return rc;
-    int nhot;
-    int64_t hb, hbytes;
-    et::hot_sizes(descs, ntables, &nhot, &hb, &hbytes);
-    int64_t ec_occ, eh_occ;
-    const et::EcList ec = et::ec_list(descs, ntables, &ec_occ);
-    const et::EcList eh = et::ec_list(descs, ntables, &eh_occ, true);
-    *bytes = et::carve_update_ws(nullptr, n, pdim, et::kChunk, nhot, hb, hbytes, &ec, ec_occ, &eh,
-                                 eh_occ).bytes;
+    *bytes = et::plan_update(descs, ntables, n, pdim, nullptr).ws.bytes;
     return ET_OK;
 }
 
@@ -3361,13 +3369,14 @@ static int sparse_sgd(int dtype, const et_update_desc* descs, int32_t ntables, d
     const bool apply_only = (flags & ET_FLAG_SGD_APPLY_ONLY) != 0;
     if (index_only && apply_only)
         return et::fail(ET_ERR_ARG, "sparse SGD: INDEX_ONLY and APPLY_ONLY both set");
-    int64_t n;
+    et::SgdRun run;
     uint64_t rows;
-    int pdim;
-    int rc = et::validate_update(descs, ntables, &n, &rows, &pdim, !index_only);
+    int rc = et::validate_update(descs, ntables, &run.n, &rows, &run.pdim, !index_only);
     if (rc != ET_OK) return rc;
-    if (n == 0) return ET_OK;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (run.n == 0) return ET_OK;
+    run.ntables = ntables;
+    run.eta64 = eta;
+    run.s = static_cast<hipStream_t>(stream);
     // Exact mode (ET_FLAG_EXACT_UPDATE, and since ABI v9 ET_FLAG_EXACT_IF_FAST too: the chain
     // path covers every element type and gradient size): every column's gradient summed
     // serially in occurrence order, as the reference does.  Columns longer than a chunk are
@@ -3376,31 +3385,24 @@ static int sparse_sgd(int dtype, const et_update_desc* descs, int32_t ntables, d
     // every column in one chunk instead (a chunk then spans a whole segment: exact, one wave
     // per column).
     const bool exact = (flags & (ET_FLAG_EXACT_UPDATE | ET_FLAG_EXACT_IF_FAST)) != 0;
-    bool chain = exact;
-    for (int t = 0; t < ntables && chain; ++t)
-        if (descs[t].batch > et::kChainMaxBatch) chain = false;
+    run.chain = exact;
+    for (int t = 0; t < ntables && run.chain; ++t)
+        if (descs[t].batch > et::kChainMaxBatch) run.chain = false;
     // chain mode: a column of at most kExactChunk occurrences is one chunk of the chunk pass
     // (a lane group's serial sum), a longer one a chain
-    const uint32_t chunk = exact && !chain ? (uint32_t)(n < 0x7fffffff ? n + 1 : 0x7fffffff)
-                           : chain          ? et::kExactChunk
-                                            : et::kChunk;
-    int nhot;
-    int64_t hb, hbytes;
-    uint64_t soff[ET_MAX_TABLES_PER_LAUNCH];
-    et::hot_sizes(descs, ntables, &nhot, &hb, &hbytes, soff);
-    int64_t ec_occ, eh_occ;
-    const et::EcList ec = et::ec_list(descs, ntables, &ec_occ);
-    const et::EcList eh = et::ec_list(descs, ntables, &eh_occ, true);
-    et::UpdateWs w = et::carve_update_ws(static_cast<char*>(workspace), n, pdim, et::kChunk,
-                                         nhot, hb, hbytes, &ec, ec_occ, &eh, eh_occ);
-    if (!workspace || ws_bytes < w.bytes)
+    run.chunk = exact && !run.chain ? (uint32_t)(run.n < 0x7fffffff ? run.n + 1 : 0x7fffffff)
+                : run.chain         ? et::kExactChunk
+                                    : et::kChunk;
+    const et::UpdatePlan plan =
+        et::plan_update(descs, ntables, run.n, run.pdim, static_cast<char*>(workspace));
+    run.w = plan.ws;
+    if (!workspace || ws_bytes < run.w.bytes)
         return et::fail(ET_ERR_WORKSPACE, "workspace of %lld bytes needed",
-                        (long long)w.bytes);
+                        (long long)run.w.bytes);
 
-    et::UpdatePack pack;
+    et::UpdatePack& pack = run.pack;
     uint32_t ro = 0, oo = 0;
-    et::VecGroups vg;
-    bool any_generic = false;
+    run.any_generic = false;
     uint32_t hot_mask = 0;
     pack.vec_mask = 0;
     for (int t = 0; t < ntables; ++t) {
@@ -3427,117 +3429,81 @@ static int sparse_sgd(int dtype, const et_update_desc* descs, int32_t ntables, d
                                             "phase needs a 16-byte aligned gradient (ld %% 4 == 0)", t);
             if (index_only || delta_ok) hot_mask |= 1u << t;
         }
-        if (table_ok && (delta_ok || index_only) && vg.add(cap, t)) {
+        if (table_ok && (delta_ok || index_only) && run.vg.add(cap, t)) {
             pack.vec_mask |= 1u << t;
         } else {
-            any_generic = true;
+            run.any_generic = true;
         }
     }
     pack.row_off[ntables] = ro;
     pack.occ_off[ntables] = oo;
-    const uint32_t sent = ro;  // key of out-of-range occurrences (sorts last)
+    run.sent = ro;  // key of out-of-range occurrences (sorts last)
 
-    et::HotList hl;
-    hl.n = 0;
+    run.hl.n = 0;
     for (int t = 0; t < ntables; ++t)
         if ((hot_mask >> t) & 1u) {
-            hl.soff[hl.n] = soff[t];
-            hl.t[hl.n++] = t;
+            run.hl.soff[run.hl.n] = plan.hot.soff[t];
+            run.hl.t[run.hl.n++] = t;
         }
     // exact mode: the chains run on three side streams — the early chains (small tables) and
     // the early hot columns (the big tables' hottest, sampled), both planned from the index
     // arrays from the start of the call, and the regular ones once the index phase has
     // planned them
-    const bool use_ec = chain && ec.n > 0;
-    const bool use_eh = chain && eh.n > 0;
+    const et::EcList &ec = plan.ec, &eh = plan.eh;
+    const bool use_ec = run.chain && ec.n > 0;
+    const bool use_eh = run.chain && eh.n > 0;
     const et::EhMap ehm = et::eh_map(use_eh ? eh : et::EcList{});
-    et::SideStreams* sides = chain ? et::side_streams() : nullptr;
-    if (chain && !sides) return et::fail(ET_ERR_HIP, "sparse SGD: side streams unavailable");
-    et::SideFork fork(sides, s);
-    // ET_WORK_STREAM=1 (experiment builds): the main-line work on a library stream
-    if (chain && ET_KNOB("ET_WORK_STREAM", 0)) {
-        s = fork.fork(et::SideStreams::kWork);
-        if (!s) return et::fail(ET_ERR_HIP, "sparse SGD: side stream fork failed");
-    }
-    hipStream_t ec_side = nullptr;
+    et::SideStreams* sides = run.chain ? et::side_streams() : nullptr;
+    if (run.chain && !sides) return et::fail(ET_ERR_HIP, "sparse SGD: side streams unavailable");
+    et::SideFork fork(sides, run.s);
     if (use_ec) {
-        ec_side = fork.fork(et::SideStreams::kEc);
-        if (!ec_side) return et::fail(ET_ERR_HIP, "sparse SGD: side stream fork failed");
+        run.cr.ec_side = fork.fork(et::SideStreams::kEc);
+        run.cr.ec_ncols = ec.col0[ec.n];
+        if (!run.cr.ec_side) return et::fail(ET_ERR_HIP, "sparse SGD: side stream fork failed");
         if (!apply_only) {
-            rc = et::launch_ec_plan(pack, ec, chunk, w.ec, nullptr, (pdim + 63) / 64, ec_side);
+            rc = et::launch_ec_plan(pack, ec, run.chunk, run.w.ec, nullptr, run.slices(),
+                                    run.cr.ec_side);
             if (rc != ET_OK) return rc;
         }
     }
-    hipStream_t eh_side = nullptr;
     if (use_eh) {
-        eh_side = fork.fork(et::SideStreams::kEh);
-        if (!eh_side) return et::fail(ET_ERR_HIP, "sparse SGD: side stream fork failed");
+        run.cr.eh_side = fork.fork(et::SideStreams::kEh);
+        run.cr.eh_ncols = eh.col0[eh.n];
+        if (!run.cr.eh_side) return et::fail(ET_ERR_HIP, "sparse SGD: side stream fork failed");
         if (!apply_only) {
-            rc = et::launch_ec_plan(pack, eh, chunk, w.eh, w.eh_cand, (pdim + 63) / 64, eh_side,
-                                    sides->cand);
+            rc = et::launch_ec_plan(pack, eh, run.chunk, run.w.eh, run.w.eh_cand, run.slices(),
+                                    run.cr.eh_side, sides->cand);
             if (rc != ET_OK) return rc;
         }
     }
-    et::Grouped gr;
     if (apply_only) {
-        gr = et::grouped_pairs(pack, ntables, w);  // phase 1 ran earlier in stream order
+        run.gr = et::grouped_pairs(pack, ntables, run.w);  // phase 1 ran earlier in stream order
     } else {
-        rc = et::group_occurrences(pack, ntables, n, sent, chunk, w, gr, s, hot_mask, &hl, chain,
-                                   use_ec ? ec.mask : 0u, snaps);
+        rc = et::group_occurrences(pack, ntables, run.n, run.sent, run.chunk, run.w, run.gr, run.s,
+                                   hot_mask, &run.hl, snaps);
         if (rc != ET_OK) return rc;
     }
-    et::ChainRun cr;
-    if (chain) {
-        cr.ec_side = ec_side;
-        cr.ec_ncols = use_ec ? ec.col0[ec.n] : 0u;
-        cr.eh_side = eh_side;
-        cr.eh_ncols = use_eh ? eh.col0[eh.n] : 0u;
-        // the regular chains' plan: on their side stream beside the chunk pass (default), or
-        // on the caller's stream before it (ET_PLAN_SIDE=0 in an experiment build: the chains
-        // start earlier, the chunk pass later; 4.13-4.16 vs 4.07 ms, round 4)
-        const bool plan_side = ET_KNOB("ET_PLAN_SIDE", 1) != 0;
-        if (!apply_only && !plan_side) {
-            rc = et::launch_chain_plan(pack, ntables, n, sent, chunk, w, gr, s,
-                                       use_ec ? ec.mask : 0u, ehm, sides->cand);
-            if (rc != ET_OK) return rc;
-        }
-        // after the index phase's chunk records (and the plan), on the work stream
-        cr.side = fork.fork(et::SideStreams::kReg, s);
-        if (!cr.side) return et::fail(ET_ERR_HIP, "sparse SGD: side stream fork failed");
-        if (!apply_only && plan_side) {
-            rc = et::launch_chain_plan(pack, ntables, n, sent, chunk, w, gr, cr.side,
-                                       use_ec ? ec.mask : 0u, ehm, sides->cand);
+    if (run.chain) {
+        // the regular chains' side stream forks after the index phase's chunk records; their
+        // plan runs on it, beside the caller's stream's chunk pass
+        run.cr.side = fork.fork(et::SideStreams::kReg);
+        if (!run.cr.side) return et::fail(ET_ERR_HIP, "sparse SGD: side stream fork failed");
+        if (!apply_only) {
+            rc = et::launch_chain_plan(pack, ntables, run.n, run.sent, run.chunk, run.w, run.gr,
+                                       run.cr.side, use_ec ? ec.mask : 0u, ehm, sides->cand);
             if (rc != ET_OK) return rc;
         }
     }
     if (index_only) return ET_OK;
 
-    const bool nt = (flags & ET_FLAG_NONTEMPORAL) != 0;
-    const int mode = (flags & ET_FLAG_SGD_UNFUSED) ? ((flags & ET_FLAG_SGD_F64_ALPHA) ? 2 : 1) : 0;
+    run.grid = et::sgd_grid(run.n);
     const double eta_c = et::convert_eta(dtype, eta);
-    const unsigned grid = et::sgd_grid(n);
-    switch (dtype) {
-        case ET_F32:
-            return et::launch_sgd_dtype<float, float>(pack, ntables, gr, w, chunk, pdim, sent,
-                                                      eta_c, eta, mode, nt, vg, any_generic, s,
-                                                      hl, grid, chain, cr);
-        case ET_F64:
-            return et::launch_sgd_dtype<double, double>(pack, ntables, gr, w, chunk, pdim, sent,
-                                                         eta_c, eta, mode, nt, vg, any_generic,
-                                                         s, hl, grid, chain, cr);
-        case ET_BF16:
-            return et::launch_sgd_dtype<__bf16, float>(pack, ntables, gr, w, chunk, pdim, sent,
-                                                       eta_c, eta, mode, nt, vg, any_generic, s,
-                                                       hl, grid, chain, cr);
-        default:  // ET_F16
-            if (flags & ET_FLAG_F16_FP32_ACC)
-                return et::launch_sgd_dtype<_Float16, float>(pack, ntables, gr, w, chunk, pdim,
-                                                             sent, eta_c, eta, mode, nt, vg,
-                                                             any_generic, s, hl, grid, chain, cr);
-            return et::launch_sgd_dtype<_Float16, _Float16>(pack, ntables, gr, w, chunk, pdim,
-                                                            sent, eta_c, eta, mode, nt, vg,
-                                                            any_generic, s, hl, grid, chain, cr);
-    }
+    return et::dispatch_sgd(dtype, flags, [&](auto e, auto mode, auto nt) {
+        using T = typename decltype(e)::type;
+        using C = typename decltype(e)::acc;
+        return et::launch_sgd_typed<T, C, decltype(mode)::value, decltype(nt)::value>(run,
+                                                                                       (C)eta_c);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -3618,7 +3584,7 @@ struct IndexWs {
 
 inline IndexWs carve_index_ws(char* base, int64_t n) {
     IndexWs w;
-    w.u = carve_update_ws(base, n, 0, kChunk);
+    w.u = plan_index_ws(base, n);
     int64_t off = w.u.bytes;
     auto take = [&](int64_t bytes) -> char* {
         char* p = base ? base + off : nullptr;
@@ -3743,30 +3709,6 @@ __global__ __launch_bounds__(256) void k_update_indexed(
     }
 }
 
-template <typename T, typename C>
-int launch_update_indexed(void* table, int64_t ld_table, int64_t cols_per_page, int64_t nrows,
-                          int dim, const void* delta, int64_t ld_delta, const int64_t* cum_col,
-                          const int64_t* cum_off, int64_t ubegin, int64_t uend,
-                          const int64_t* map, double eta_c, double eta, int mode, bool nt,
-                          hipStream_t s) {
-    const int64_t nb = cdiv64(uend - ubegin, 4);
-    const unsigned grid = (unsigned)(nb < 8192 ? nb : 8192);
-#define ET_UI(M, NTV)                                                                           \
-    hipLaunchKernelGGL((k_update_indexed<T, C, M, NTV>), dim3(grid), dim3(256), 0, s, table,   \
-                       ld_table, cols_per_page, nrows, dim, (const T*)delta, ld_delta, cum_col, \
-                       cum_off, ubegin, uend, map, (C)eta_c, eta)
-    if (mode == 0) {
-        if (nt) ET_UI(0, true); else ET_UI(0, false);
-    } else if (mode == 1) {
-        if (nt) ET_UI(1, true); else ET_UI(1, false);
-    } else {
-        if (nt) ET_UI(2, true); else ET_UI(2, false);
-    }
-#undef ET_UI
-    ET_LAUNCH_CHECK("k_update_indexed");
-    return ET_OK;
-}
-
 }  // namespace et
 
 extern "C" int et_update_indexed(int dtype, void* table, int64_t ld_table,
@@ -3785,22 +3727,19 @@ extern "C" int et_update_indexed(int dtype, void* table, int64_t ld_table,
     if (!table || !delta || !cumulative_col || !cumulative_off || !map)
         return et::fail(ET_ERR_ARG, "NULL argument");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool nt = (flags & ET_FLAG_NONTEMPORAL) != 0;
-    const int mode = (flags & ET_FLAG_SGD_UNFUSED) ? ((flags & ET_FLAG_SGD_F64_ALPHA) ? 2 : 1) : 0;
     const double eta_c = et::convert_eta(dtype, eta);
-#define ET_UI_T(T, C)                                                                     \
-    return et::launch_update_indexed<T, C>(table, ld_table, cols_per_page, nrows, dim, delta, \
-                                           ld_delta, cumulative_col, cumulative_off, ubegin,  \
-                                           uend, map, eta_c, eta, mode, nt, s)
-    switch (dtype) {
-        case ET_F32: ET_UI_T(float, float);
-        case ET_F64: ET_UI_T(double, double);
-        case ET_BF16: ET_UI_T(__bf16, float);
-        default:
-            if (flags & ET_FLAG_F16_FP32_ACC) ET_UI_T(_Float16, float);
-            ET_UI_T(_Float16, _Float16);
-    }
-#undef ET_UI_T
+    const int64_t nb = et::cdiv64(uend - ubegin, 4);
+    const unsigned grid = (unsigned)(nb < 8192 ? nb : 8192);
+    return et::dispatch_sgd(dtype, flags, [&](auto e, auto mode, auto nt) {
+        using T = typename decltype(e)::type;
+        using C = typename decltype(e)::acc;
+        hipLaunchKernelGGL((et::k_update_indexed<T, C, decltype(mode)::value, decltype(nt)::value>),
+                           dim3(grid), dim3(256), 0, s, table, ld_table, cols_per_page, nrows, dim,
+                           (const T*)delta, ld_delta, cumulative_col, cumulative_off, ubegin, uend,
+                           map, (C)eta_c, eta);
+        ET_LAUNCH_CHECK("k_update_indexed");
+        return (int)ET_OK;
+    });
 }
 
 // Ragged gradients (et_ragged_sgd, et_ragged_bag_ids): kernels and entry points.

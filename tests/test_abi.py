@@ -99,6 +99,43 @@ def test_argument_errors_need_no_gpu():
     assert L.et_sgd_workspace_size(ctypes.addressof(big), 33, ctypes.byref(nb)) == -1
 
 
+def test_workspace_check_agrees_with_the_size_told():
+    """et_sgd_workspace_size and et_sparse_sgd's own check come from one computation
+    (plan_update, csrc/et_update.hip).  The size told carries 256 bytes of slack for the
+    layout's alignment; a call whose workspace starts `pad` bytes before a 256-byte boundary
+    needs size - 256 + pad of them.  One byte less is ET_ERR_WORKSPACE, its message names
+    exactly that number, and the check comes before any launch (the dummy pointers here are
+    never dereferenced: every call below fails it).  Like test_phase_flags_need_no_gpu, the
+    calls do pass through et::open_side_streams first: without a device its hipGetDevice
+    fails and it returns; with one it opens the library's three side streams, as any first
+    call does."""
+    from embtab import _lib
+
+    L = _lib.load()
+    P = 1 << 20  # dummy table / gradient / index address
+
+    def desc(nrows, dim, pool, batch):
+        return _lib.UpdateDesc(P, dim, nrows, dim, pool, P, dim, P, pool, batch)
+
+    shapes = {
+        "smoke": [desc(1000, 16, 20, 128), desc(777, 128, 20, 128), desc(50, 64, 20, 128)],
+        "hot beside dim 64": [desc(100000, 128, 20, 4096), desc(5000, 64, 40, 4096)],
+        "dim 10, early-chain rows": [desc(100, 10, 3, 1000)],
+    }
+    for name, tables in shapes.items():
+        d = (_lib.UpdateDesc * len(tables))(*tables)
+        nb = ctypes.c_int64(0)
+        assert L.et_sgd_workspace_size(ctypes.addressof(d), len(tables), ctypes.byref(nb)) == 0
+        size = nb.value
+        for base, pad in ((1 << 24, 0), ((1 << 24) + 1, 255), ((1 << 24) + 192, 64)):
+            need = size - 256 + pad
+            for flags in (0, _lib.ET_FLAG_EXACT_UPDATE):
+                rc = L.et_sparse_sgd(_lib.ET_F32, ctypes.addressof(d), len(tables), 0.1, flags,
+                                     ctypes.c_void_p(base), need - 1, None)
+                assert rc == -3, (name, base, flags, L.et_last_error())
+                assert re.search(rb"\b%d bytes" % need, L.et_last_error()), (name, base, need)
+
+
 def test_phase_flags_need_no_gpu():
     """ET_FLAG_SGD_INDEX_ONLY / APPLY_ONLY are exclusive; INDEX_ONLY accepts NULL
     gradients (it never reads them) but still validates the index arrays; the workspace

@@ -76,5 +76,8 @@ def test_wrong_result_knob_and_dead_walks_are_gone():
     src = "".join(open(os.path.join(CSRC, f)).read() for f in os.listdir(CSRC)
                   if f.endswith((".hip", ".h", ".cpp")))
     for gone in ("ET_CHAIN_FAKE", "ET_CHAIN_FED", "ET_CHAIN_RING", "chain_walk_ring",
-                 "fed_gather_asm", "k_sgd_chains_fed", "hf_pair"):
+                 "fed_gather_asm", "k_sgd_chains_fed", "hf_pair",
+                 # the losing variants of the update pipeline (DESIGN.md keeps their numbers)
+                 "k_sgd_chains_w", "ET_EH_WIDE", "ET_WORK_STREAM", "ET_PLAN_SIDE", "ET_SGD_OCC5",
+                 "ET_SGD_SINGLES", "ET_SIDE_HIGH", "kWork"):
         assert gone not in src, gone
