@@ -600,6 +600,12 @@ struct StripeMap {
     int prio;
     int nheavy;            // entry[x][0, nheavy): the heavy tables (> light_bytes)
     int qorder;            // queued schedule: 1 = every heavy item before the light ones
+    // queued schedule, class preference of a workgroup (k_pooled_vec_queued): 0 = none (one
+    // queue per XCD), 1 = policy A (fab_share sixteenths of the CUs prefer the fabric class),
+    // 2 = policy B (at most cache_cap cache workgroups resident per XCD)
+    int affinity;
+    int fab_share;
+    int cache_cap;
 };
 
 template <typename T, typename A, int D, int U, bool NT, bool NTI, bool SG = false, int NA = 0>
@@ -714,12 +720,70 @@ __global__ __launch_bounds__(256) void k_pooled_vec_striped(LookupPack pack, Str
 // a per-thread default stream, a re-created stream handle or another device's
 // stream could share one).  Which workgroup sums which bags never changes a result:
 // bit-identical to the static schedule.
+//
+// CU affinity (two class queues per XCD).  An XCD's entries are [0, nheavy): the FABRIC class
+// (tables above light_bytes, whose rows cross the fabric wherever they are read) and
+// [nheavy, nent): the CACHE class (light tables served by this XCD's L2).  With a preference
+// policy (sm.affinity != 0) every XCD has one head per class and a workgroup claims in this
+// order, x being the XCD it runs on:
+//   cache-preferring:   cache(x), fabric(x), fabric(other XCDs), cache(other XCDs)
+//   fabric-preferring:  fabric(x), fabric(other XCDs), cache(x), cache(other XCDs)
+// (a cache item run on a foreign XCD misses that XCD's L2 and adds fabric bytes; a fabric item
+// costs the same anywhere, so foreign cache items come last).  Within a class the items keep
+// the static order (class slot h -> j = h / n_class, k = h % n_class).  Every workgroup tries
+// all 16 heads before giving up, heads only grow, and the grid has exactly as many workgroups
+// as items, so a workgroup that found every head exhausted would mean more than `items`
+// claims succeeded — impossible: every workgroup finds one, and none ever waits for another.
+// Without a policy (affinity 0: a class is empty, or fab_share 0) head[x][0] is the one queue of
+// XCD x over all its items, exactly the schedule described above.
+//   policy A (the default, fab_share 8): a workgroup prefers the fabric class iff a fixed hash
+//     of its CU (SE, SH, CU fields of HW_REG_HW_ID) is below fab_share sixteenths.  On a CU
+//     with no fabric-class neighbour a light workgroup lasts 42 us instead of 57 (a light
+//     workgroup's L2 hits return no sooner than the fabric round trips queued ahead of them on
+//     a shared CU); headline 1.212 vs 1.226 ms for the parent, shares 6 / 7 / 9 / 10 / 12 at
+//     1.26 / 1.22 / 1.24 / 1.33 / 1.73 (profiles/r07/cu_affinity/, DESIGN §4 "CU affinity");
+//   policy B (experiment builds, ET_AFFINITY=B): a workgroup prefers the cache class while
+//     fewer than cache_cap cache workgroups are resident on its XCD (resident[x], counted at
+//     the claim, released by thread 0 when the cache item ends) — 2.1-2.5 ms, dropped.
 struct XcdQueue {
-    uint32_t head[kXcds];
+    uint32_t head[kXcds][2];    // [x][0]: fabric class (or the whole queue); [x][1]: cache class
     uint32_t done;
-    uint32_t pad[32 - kXcds - 1];  // one 128-byte line
+    uint32_t resident[kXcds];   // policy B: cache workgroups running on XCD x
+    uint32_t pad[32 - 3 * kXcds - 1];  // one 128-byte line
 };
 static_assert(sizeof(XcdQueue) == ET_LOOKUP_QUEUE_BYTES, "queue block size (include/embtab.h)");
+
+// 4-bit bit reversal of a CU label: consecutive CU ids alternate between the two kinds at every
+// share, and the SE / SH terms stagger the pattern between shader engines, so harvested
+// (missing) CU ids shift the share of fabric CUs by at most one CU per shader engine.
+__device__ __forceinline__ uint32_t cu_hash16(uint32_t hw) {
+    const uint32_t cu = (hw >> 8) & 15u, sh = (hw >> 12) & 1u, se = (hw >> 13) & 7u;
+    const uint32_t v = (cu + 3u * se + 5u * sh) & 15u;
+    return ((v & 1u) << 3) | ((v & 2u) << 1) | ((v & 4u) >> 1) | ((v & 8u) >> 3);
+}
+
+// One claim from class c of XCD x: the item (x * per + its slot in the static order) or ~0u.
+__device__ __forceinline__ uint32_t claim_class(XcdQueue& q, uint32_t x, uint32_t c,
+                                                uint32_t nheavy, uint32_t ntables, uint32_t sc) {
+    const uint32_t nk = c ? ntables - nheavy : nheavy;
+    const uint32_t h = atomicAdd(&q.head[x][c], 1u);
+    if (h >= nk * sc) return ~0u;
+    return x * (ntables * sc) + (h / nk) * ntables + (c ? nheavy : 0u) + h % nk;
+}
+
+// The claim order above for a workgroup on XCD x0 that prefers class p.
+__device__ __forceinline__ uint32_t claim_pref(XcdQueue& q, uint32_t x0, uint32_t p,
+                                               uint32_t nheavy, uint32_t ntables, uint32_t sc) {
+    constexpr uint32_t M = (uint32_t)(kXcds - 1);
+    uint32_t it = claim_class(q, x0, p, nheavy, ntables, sc);
+    if (it == ~0u && p == 1u) it = claim_class(q, x0, 0u, nheavy, ntables, sc);
+    for (uint32_t k = 1; it == ~0u && k < (uint32_t)kXcds; ++k)
+        it = claim_class(q, (x0 + k) & M, 0u, nheavy, ntables, sc);
+    if (it == ~0u && p == 0u) it = claim_class(q, x0, 1u, nheavy, ntables, sc);
+    for (uint32_t k = 1; it == ~0u && k < (uint32_t)kXcds; ++k)
+        it = claim_class(q, (x0 + k) & M, 1u, nheavy, ntables, sc);
+    return it;
+}
 
 template <typename T, typename A, int D, int U, bool NT, bool SG, int NA = 0>
 __global__ __launch_bounds__(256) void k_pooled_vec_queued(LookupPack pack, StripeMap sm,
@@ -727,6 +791,9 @@ __global__ __launch_bounds__(256) void k_pooled_vec_queued(LookupPack pack, Stri
                                                            T* __restrict__ dst, int64_t ld_dst,
                                                            int rounds, int64_t stripe_chunks,
                                                            int64_t nchunks) {
+#ifdef ET_WG_TIMELINE
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+#endif
     __shared__ uint32_t s_item;
     XcdQueue& q = *pack.queue;
     const uint32_t per = (uint32_t)(ntables * stripe_chunks);  // items per XCD
@@ -734,9 +801,33 @@ __global__ __launch_bounds__(256) void k_pooled_vec_queued(LookupPack pack, Stri
         uint32_t xcc;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         uint32_t it = ~0u;
+        if (sm.affinity != 0) {
+            const uint32_t x0 = xcc & (uint32_t)(kXcds - 1);
+            const uint32_t nh = (uint32_t)sm.nheavy, sc = (uint32_t)stripe_chunks;
+            uint32_t hw;
+            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+            uint32_t p = cu_hash16(hw) < (uint32_t)sm.fab_share ? 0u : 1u;  // policy A
+#ifdef ET_EXPERIMENTS
+            uint32_t counted = 0u;
+            if (sm.affinity == 2) {  // policy B
+                counted = atomicAdd(&q.resident[x0], 1u) < (uint32_t)sm.cache_cap ? 1u : 0u;
+                if (!counted) atomicSub(&q.resident[x0], 1u);
+                p = counted;
+            }
+#endif
+            it = claim_pref(q, x0, p, nh, (uint32_t)ntables, sc);
+#ifdef ET_EXPERIMENTS
+            if (sm.affinity == 2) {
+                // resident[x0] counts the workgroups that run a cache item on x0
+                const bool cache = it != ~0u && (it % per) % (uint32_t)ntables >= nh;
+                if (cache && !counted) atomicAdd(&q.resident[x0], 1u);
+                if (!cache && counted) atomicSub(&q.resident[x0], 1u);
+            }
+#endif
+        } else
         for (uint32_t k = 0; k < (uint32_t)kXcds; ++k) {
             const uint32_t x = (xcc + k) & (uint32_t)(kXcds - 1);
-            const uint32_t h = atomicAdd(&q.head[x], 1u);
+            const uint32_t h = atomicAdd(&q.head[x][0], 1u);
             if (h < per) {
                 it = x * per + h;
                 break;
@@ -749,7 +840,9 @@ __global__ __launch_bounds__(256) void k_pooled_vec_queued(LookupPack pack, Stri
     if (it != ~0u) {
         int64_t slot = (int64_t)(it % per);
 #ifdef ET_EXPERIMENTS
-        if (sm.qorder == 1 && sm.nheavy > 0 && sm.nheavy < ntables) {
+        if (sm.affinity != 0) {
+            // the class queues keep the static order within each class (claim_class)
+        } else if (sm.qorder == 1 && sm.nheavy > 0 && sm.nheavy < ntables) {
             // heavy-first: the queue's first nheavy * stripe_chunks items are the heavy
             // tables' chunks, then the light ones (slot = j * ntables + k, as the static order)
             const int64_t hn = (int64_t)sm.nheavy * stripe_chunks;
@@ -766,9 +859,39 @@ __global__ __launch_bounds__(256) void k_pooled_vec_queued(LookupPack pack, Stri
         striped_body<T, A, D, U, NT, false, SG, NA>(pack, sm, ntables, batch, dst, ld_dst, rounds,
                                                     stripe_chunks, nchunks, (int)(it / per), slot);
     }
+#ifdef ET_WG_TIMELINE
+    // Profiling build only (tools/wg_timeline.sh): the stamps of k_pooled_vec_striped, with the
+    // claimed item's table and home XCD
+    __syncthreads();
+    if (threadIdx.x == 0 && blockIdx.x < kTlCap) {
+        const uint64_t t1 = __builtin_amdgcn_s_memrealtime();
+        uint32_t xcc, hw;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+        uint32_t t = 0xffu;
+        if (it != ~0u) {
+            const int64_t slot = (int64_t)(it % per);
+            const uint32_t e = sm.entry[it / per][slot % ntables];
+            const int64_t chunk = (int64_t)((e >> 8) & 0xff) * stripe_chunks + slot / ntables;
+            t = (chunk >= nchunks ? 0xffu : (e & 0xffu)) | ((it / per) << 8);
+        }
+        g_tl[blockIdx.x][0] = make_uint4((uint32_t)t0, (uint32_t)(t0 >> 32), (uint32_t)t1,
+                                         (uint32_t)(t1 >> 32));
+        g_tl[blockIdx.x][1] = make_uint4(t, xcc, hw, gridDim.x);
+    }
+#endif
+#ifdef ET_EXPERIMENTS
+    if (threadIdx.x == 0 && sm.affinity == 2 && it != ~0u &&
+        (it % per) % (uint32_t)ntables >= (uint32_t)sm.nheavy) {
+        uint32_t xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        atomicSub(&q.resident[xcc & (uint32_t)(kXcds - 1)], 1u);
+        __threadfence();  // the release lands before this workgroup counts as done (the reset)
+    }
+#endif
     if (threadIdx.x == 0 && atomicAdd(&q.done, 1u) == gridDim.x - 1u) {  // the last one
-        for (int x = 0; x < kXcds; ++x) atomicExch(&q.head[x], 0u);
-        atomicExch(&q.done, 0u);
+        uint32_t* w = reinterpret_cast<uint32_t*>(&q);
+        for (int i = 0; i < (int)(sizeof(XcdQueue) / sizeof(uint32_t)); ++i) atomicExch(&w[i], 0u);
     }
 }
 
@@ -1165,6 +1288,12 @@ struct LookupTuning {
     int heavy_prio = 0;            // ET_HEAVY_PRIO=1: heavy tables' waves at priority 2
     int qorder = 0;                // ET_QORDER=1: queued schedule, heavy items first
     int noadd = 0;                 // ET_HEAD_NOADD=1: the scalar loop without its adds
+    // Class preference of the queued schedule's workgroups (k_pooled_vec_queued, "CU affinity"):
+    // ET_AFFINITY=0|A|B, ET_FAB_SHARE (policy A, sixteenths of the CUs that prefer the fabric
+    // class; 0 = no preference), ET_CACHE_CAP (policy B, cache workgroups resident per XCD)
+    int affinity = 1;              // policy A
+    int fab_share = 8;             // the sweep's choice (profiles/r07/cu_affinity/sweep.txt)
+    int cache_cap = 64;
     // Tables of (light_bytes, fsplit_bytes] cut into fsplit_g feature groups, group g on XCDs
     // [g * 8 / G, (g + 1) * 8 / G), so each XCD's L2 holds 1/G of the table (ET_FSPLIT_*)
     int64_t fsplit_bytes = 0;
@@ -1192,6 +1321,10 @@ inline const LookupTuning& tuning() {
         v.sg256 = (int)ET_KNOB("ET_SG256", v.sg256);
         v.heavy_prio = (int)ET_KNOB("ET_HEAVY_PRIO", v.heavy_prio);
         v.qorder = (int)ET_KNOB("ET_QORDER", v.qorder);
+        if (const char* e = getenv("ET_AFFINITY"))
+            v.affinity = *e == 'A' ? 1 : *e == 'B' ? 2 : 0;
+        v.fab_share = (int)ET_KNOB("ET_FAB_SHARE", v.fab_share);
+        v.cache_cap = (int)ET_KNOB("ET_CACHE_CAP", v.cache_cap);
         v.fsplit_bytes = ET_KNOB("ET_FSPLIT_BYTES", v.fsplit_bytes);
         const int g = (int)ET_KNOB("ET_FSPLIT_G", 4);
         v.fsplit_g = g == 2 || g == 8 ? g : 4;
@@ -1262,6 +1395,12 @@ inline void build_stripe_map(const LookupPack& pack, int n, int es, StripeMap& s
         sm.entry[x][cnt[x]++] = (uint32_t)order[q / kXcds] | ((uint32_t)(q % kXcds) << 8);
     }
     sm.nent = cnt[0];
+    // a class preference needs both classes (and, policy A, a share to prefer by): otherwise
+    // none, the one-queue schedule
+    sm.affinity = sm.nheavy > 0 && sm.nheavy < sm.nent ? tu.affinity : 0;
+    sm.fab_share = tu.fab_share < 0 ? 0 : tu.fab_share > 16 ? 16 : tu.fab_share;
+    sm.cache_cap = tu.cache_cap < 0 ? 0 : tu.cache_cap;
+    if (sm.affinity == 1 && sm.fab_share == 0) sm.affinity = 0;
 }
 
 template <typename T, typename A, int D, int U, bool NT, bool PG = false, bool MK = false>

@@ -14,7 +14,10 @@
 #   cfg2             config 2: kernel trace (graph and eager: duration vs gap) + PMC traffic
 #   classpmc         PMC traffic + time of each headline table class alone (tools/class_pmc.py)
 #   lookab:LIB:S1/S2:N  the headline launch (kernel ms) with library LIB and env sets S1, S2
-#                    (VAR=V,VAR=V; NONE=0 for none), alternating N times
+#                    (VAR=V,VAR=V; NONE=0 for none), alternating N times; a set LIB=NAME[,VAR=V..]
+#                    runs with tools/alt/libembtab_hip_NAME.so; lookab:LIB:SETS:N:STEPS sets --steps
+#   exptests:VAR=V,..:EXPR  pytest -m gpu -k EXPR with the experiment build and env VAR=V
+#   tl:LIB:NAME[:VAR=V,..]  per-workgroup timeline (tools/wg_timeline.py) of profiling build LIB
 #   expexact:VAR=V,..  the exact step with the experiment build and env VAR=V
 #   upd:N            the config-4 update alone, N processes (tools/upd_only.py)
 #   ab:A:B:N         the config-4 update with library builds A and B (paths), alternating N times
@@ -31,7 +34,7 @@ cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 LIB=embeddingtables.jl_amd/embtab/libembtab_hip.so
-EXP=tools/exp/libembtab_hip_exp.so
+EXP=${ET_EXP_LIBRARY:-tools/exp/libembtab_hip_exp.so}  # (tools/exp is not pushed by default)
 
 die() { echo "FAIL $1"; tail -25 "$2"; exit 1; }
 
@@ -134,14 +137,32 @@ print('$SETS $c', t['tables'], 'tables', round(t['ms_median'],4), 'ms', 'fabric'
       done ;;
     lookab:*)
       # the headline launch with experiment library A and env sets (VAR=V,...;VAR=V,...), N rounds
-      IFS=: read -r _ LIBV SETSALL N <<< "$step"
+      # a set that starts with LIB=NAME runs with $ET_LIB_DIR/libembtab_hip_NAME.so instead (default
+      # tools/alt; e.g. the parent commit's build beside the experiment build; NAME=shipped: the
+      # package's own); a 5th field sets --steps (default 40)
+      IFS=: read -r _ LIBV SETSALL N STEPS <<< "$step"
       for i in $(seq 1 "${N:-2}"); do
         for SETS in $(echo "$SETSALL" | tr "/" " "); do
-          env ET_LIBRARY=$LIBV $(echo "$SETS" | tr ',' ' ') timeout -k 10 200 python3 bench.py --steps 40 --warmup 5 \
+          L=$LIBV; S=$SETS
+          case "$SETS" in
+            LIB=*,*) L=${SETS%%,*}; L=${L#LIB=}; S=${SETS#*,} ;;
+            LIB=*) L=${SETS#LIB=}; S=NONE=0 ;;
+          esac
+          if [ "$L" != "$LIBV" ]; then
+            L=$([ "$L" = shipped ] && echo "$LIB" || echo "${ET_LIB_DIR:-tools/alt}/libembtab_hip_$L.so")
+          fi
+          env ET_LIBRARY=$L $(echo "$S" | tr ',' ' ') timeout -k 10 200 python3 bench.py --steps "${STEPS:-40}" --warmup 5 \
             --cpu-seconds 0 --no-extra --no-check > "$OUT/lookab.json" 2> "$OUT/lookab.err" || die lookab "$OUT/lookab.err"
-          python3 -c "import json; d=json.load(open('$OUT/lookab.json')); print('$SETS', round(d['roofline']['kernel_ms'],4), round(d['roofline']['kernel_ms_median'],4))"
+          python3 -c "import json; d=json.load(open('$OUT/lookab.json')); print('$SETS', round(d['roofline']['kernel_ms'],4), round(d['roofline']['kernel_ms_median'],4))" \
+            | tee -a "$OUT/lookab.txt"
         done
       done ;;
+    tl:*)
+      # per-workgroup timeline of the headline launch with profiling build LIB (tools/wg_timeline.sh)
+      IFS=: read -r _ LIBV NAME SETS <<< "$step"
+      env ET_TL_LIBRARY=$LIBV $(echo "${SETS:-NONE=0}" | tr ',' ' ') timeout -k 10 300 python3 tools/wg_timeline.py \
+        "$OUT/$NAME.json" > "$OUT/$NAME.txt" 2>&1 || die tl "$OUT/$NAME.txt"
+      tail -1 "$OUT/$NAME.txt" | cut -c1-4000 ;;
     expexact:*)
       SETS=${step#expexact:}; T=$OUT/exp_$(echo "$SETS" | tr ',=' '__')
       env ET_LIBRARY=$EXP $(echo "$SETS" | tr ',' ' ') timeout -k 10 300 rocprofv3 --kernel-trace --stats \
