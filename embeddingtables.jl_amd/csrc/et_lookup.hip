@@ -46,7 +46,7 @@ struct VecGeom {
     static constexpr int LPR = VPR < 64 ? VPR : 64;   // lanes per group (one row)
     static constexpr int NV = VPR / LPR;              // vectors per lane per row
     static constexpr int GPW = 64 / LPR;              // groups (bags) per wave
-    static constexpr int U = NV >= 8 ? 1 : 8 / NV;    // default rows in flight per group
+    static constexpr int U = NV >= 8 ? 1 : 8 / NV;    // rows in flight per group
     static_assert(D % N == 0, "row must be whole vectors");
     static_assert(VPR <= 64 ? (64 % VPR == 0) : (VPR % 64 == 0), "unsupported row size");
 };
@@ -65,18 +65,16 @@ __device__ __forceinline__ u32x4 pack16(const T (&x)[N]) {
 }
 
 // Broadcast the 64-bit value held by lane (g*LPR + i) to every lane of group g; i is
-// wave-uniform.  With <= ET_BCAST_READLANE_MAX_GPW groups per wave this is 2*GPW
+// wave-uniform.  With <= kBcastReadlaneMaxGpw groups per wave this is 2*GPW
 // v_readlane + selects (no LDS round trip, nothing for the waitcnt pass to serialise);
 // wider waves use ds_bpermute.  Round 4: 2 (four groups — 256-byte rows, the Float16
 // config-3 leg — take ds_bpermute: 14 VALU per row were the issue bound of its
-// L2-resident tables); -DET_BCAST_READLANE_MAX_GPW=4 restores the round-3 choice.
-#ifndef ET_BCAST_READLANE_MAX_GPW
-#define ET_BCAST_READLANE_MAX_GPW 2
-#endif
+// L2-resident tables; round 3 had 4).
+constexpr int kBcastReadlaneMaxGpw = 2;
 template <int LPR>
 __device__ __forceinline__ long long group_bcast(long long v, int i, int g) {
     constexpr int GPW = 64 / LPR;
-    if constexpr (GPW <= ET_BCAST_READLANE_MAX_GPW) {
+    if constexpr (GPW <= kBcastReadlaneMaxGpw) {
         const int lo = (int)v, hi = (int)(v >> 32);
         int rlo = __builtin_amdgcn_readlane(lo, i), rhi = __builtin_amdgcn_readlane(hi, i);
 #pragma unroll
@@ -96,7 +94,7 @@ __device__ __forceinline__ long long group_bcast(long long v, int i, int g) {
 template <int LPR>
 __device__ __forceinline__ uint32_t group_bcast32(uint32_t v, int i, int g) {
     constexpr int GPW = 64 / LPR;
-    if constexpr (GPW <= ET_BCAST_READLANE_MAX_GPW) {
+    if constexpr (GPW <= kBcastReadlaneMaxGpw) {
         int r = __builtin_amdgcn_readlane((int)v, i);
 #pragma unroll
         for (int gg = 1; gg < GPW; ++gg) {
@@ -118,14 +116,10 @@ __device__ __forceinline__ uint32_t idx_row32(long long v, uint32_t nrows) {
 
 // The first (up to) LPR indices of a bag, one per lane of the group; lanes past the
 // end re-read the last one so that no lane is masked off.
-template <int LPR, bool NTI = false>
+template <int LPR>
 __device__ __forceinline__ long long load_idx_chunk(const int64_t* __restrict__ ip, int cnt,
                                                     int sub) {
-    const int64_t* p = ip + (sub < cnt ? sub : cnt - 1);
-    if constexpr (NTI)
-        return (long long)__builtin_nontemporal_load(p);
-    else
-        return (long long)*p;
+    return (long long)ip[sub < cnt ? sub : cnt - 1];
 }
 
 // Issue UU row loads of one bag (slots i0 .. i0+UU-1 of the current index chunk, all
@@ -285,8 +279,8 @@ __device__ __forceinline__ void bag_sum_vec(const T* __restrict__ table, uint32_
 
 // `rounds` bags of one table per lane group, the next bag's first index chunk loaded
 // while the current bag's rows are in flight.
-template <typename T, typename A, int D, int U, bool NT, bool NTL, bool NTI = false,
-          bool PG = false, bool MK = false>
+template <typename T, typename A, int D, int U, bool NT, bool NTL, bool PG = false,
+          bool MK = false>
 __device__ __forceinline__ void run_bags(const et_lookup_desc& d, int64_t batch,
                                          T* __restrict__ dst, int64_t ld_dst, int64_t chunk,
                                          int rounds) {
@@ -300,50 +294,18 @@ __device__ __forceinline__ void run_bags(const et_lookup_desc& d, int64_t batch,
     const uint32_t ldt = (uint32_t)d.ld_table, nr = (uint32_t)d.nrows;
     const int vpr = MK ? d.dim / G::N : G::VPR;  // vectors per row
     int64_t bag = chunk * per_round * rounds + wave * G::GPW + g;
-    long long my_next = load_idx_chunk<G::LPR, NTI>(
+    long long my_next = load_idx_chunk<G::LPR>(
         d.idx + (bag < batch ? bag : batch - 1) * d.ld_idx, cnt0, sub);
     for (int r = 0; r < rounds; ++r) {
         if (bag >= batch) break;
         const long long my = my_next;
         const int64_t nbag = bag + per_round;
         if (r + 1 < rounds)
-            my_next = load_idx_chunk<G::LPR, NTI>(
+            my_next = load_idx_chunk<G::LPR>(
                 d.idx + (nbag < batch ? nbag : batch - 1) * d.ld_idx, cnt0, sub);
         bag_sum_vec<T, A, D, U, NT, NTL, PG, MK>(table, ldt, nr, (uint32_t)d.cols_per_page,
                                                  d.idx + bag * d.ld_idx, pool, my,
                                                  dst + bag * ld_dst + d.dst_row_off, g, sub, vpr);
-        bag = nbag;
-    }
-}
-
-// A feature slice of a bag range (the feature-split tables of the striped schedule): the
-// bags [bag0, bag1) of table d, features [fofs, fofs + DS) only — DS-feature rows at the
-// table's row stride, so each lane group reads DS * sizeof(T) bytes per row.  Sums are per
-// feature in pool order, exactly as run_bags, so the output is bit-identical however the
-// features are cut.
-template <typename T, typename A, int DS, bool NT>
-__device__ __forceinline__ void run_bags_slice(const et_lookup_desc& d, int64_t batch,
-                                               T* __restrict__ dst, int64_t ld_dst, int64_t bag0,
-                                               int64_t bag1, int fofs) {
-    using G = VecGeom<T, DS>;
-    const T* table = reinterpret_cast<const T*>(d.table) + fofs;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane / G::LPR, sub = lane % G::LPR;
-    const int64_t per_round = 4 * G::GPW;
-    const int pool = d.pool;
-    const int cnt0 = pool < G::LPR ? pool : G::LPR;
-    const uint32_t ldt = (uint32_t)d.ld_table, nr = (uint32_t)d.nrows;
-    const int64_t end = bag1 < batch ? bag1 : batch;
-    int64_t bag = bag0 + wave * G::GPW + g;
-    long long my_next = load_idx_chunk<G::LPR>(d.idx + (bag < end ? bag : end - 1) * d.ld_idx,
-                                                cnt0, sub);
-    while (bag < end) {
-        const long long my = my_next;
-        const int64_t nbag = bag + per_round;
-        if (nbag < end) my_next = load_idx_chunk<G::LPR>(d.idx + nbag * d.ld_idx, cnt0, sub);
-        bag_sum_vec<T, A, DS, G::U, NT, false>(table, ldt, nr, 0u, d.idx + bag * d.ld_idx, pool,
-                                               my, dst + bag * ld_dst + d.dst_row_off + fofs, g,
-                                               sub, G::VPR);
         bag = nbag;
     }
 }
@@ -371,32 +333,14 @@ __device__ __forceinline__ void run_bags_slice(const et_lookup_desc& d, int64_t 
 // instead of ~30 VALU per KiB) measured slower than load_add (D = 64 fp32, 8 tables,
 // B = 65536: L2-resident 0.248 vs 0.227 ms, HBM 0.539 vs 0.462 ms) — four bags' scalar
 // index loads stall each batch, where load_add prefetches the next bag's indices — so
-// only 512-byte rows take this loop.
+// only 512-byte rows take this loop.  (Round 4 tried 256-byte rows once more as two bags
+// per wave with 8-byte lanes: slower again, DESIGN.md "256-byte rows on the scalar-addressed
+// pooled loop".)
 typedef const __attribute__((address_space(4))) int64_t* cidx_ptr;
-
-// Bytes per lane of the scalar-addressed loop: 16 for 512-byte rows, 8 for 256-byte rows
-// (D = 128 fp16 / bf16, 64 fp32): two bags per wave either way — half a wave per row —
-// so both bags stay wave-uniform and their indices scalar.  (Round 2 tried 256-byte rows
-// as FOUR bags per wave with 16-byte lanes: the four scalar index streams stalled each
-// batch, and it was slower than load_add.)
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-template <int BPL> struct SgVec { typedef u32x4 type; };
-template <> struct SgVec<8> { typedef u32x2 type; };
-template <typename T> constexpr int sg_bpl(int D) { return D * (int)sizeof(T) / 32; }
-
-template <bool NT, typename V>
-__device__ __forceinline__ void store_v(V* p, V v) {
-    if constexpr (NT)
-        __builtin_nontemporal_store(v, p);
-    else
-        *p = v;
-}
 
 __device__ __forceinline__ cidx_ptr as_scalar_idx(const int64_t* p) {
     return (cidx_ptr)(uintptr_t)p;
 }
-
-typedef const __attribute__((address_space(1))) u32x4 gvec16;
 
 // Row offset of a 1-based index v (wave-uniform) in bytes: 32-bit scalar ops only
 // (gfx950's scalar ALU has no 64-bit multiply or ordered 64-bit compare); `bad` gets
@@ -414,18 +358,13 @@ __device__ __forceinline__ uint64_t row_off_s(int64_t v, uint32_t ldb, uint32_t 
 // One batch of UU rows of both bags.  Returns false — before issuing any row load —
 // if an index of the batch is out of range; the caller then redoes the bag pair with
 // bag_pair_checked.
-// NA (experiment builds only, ET_HEAD_NOADD): the same loads, waits and stores with the adds
-// replaced by an empty consumer (each loaded vector is an input of an empty asm, so its
-// load must complete there; the result is the bag's first row, not its sum) — the ceiling of
-// this schedule's byte mix without the arithmetic.
-template <typename T, typename A, int UU, bool NTL, int BPL = 16, int NA = 0>
+template <typename T, typename A, int UU, bool NTL>
 __device__ __forceinline__ bool load_add_s(uintptr_t tb, uint32_t ldb, uint32_t nrows,
                                            cidx_ptr ia, cidx_ptr ib, uint64_t hmask,
                                            uint64_t lane_off, bool first_batch,
-                                           A (&acc)[BPL / sizeof(T)]) {
-    constexpr int N = BPL / (int)sizeof(T);
-    typedef typename SgVec<BPL>::type V;
-    typedef const __attribute__((address_space(1))) V gvec;
+                                           A (&acc)[16 / sizeof(T)]) {
+    constexpr int N = 16 / (int)sizeof(T);
+    typedef const __attribute__((address_space(1))) u32x4 gvec;
     // lane address = table + row_off(A) + (hi ? row_off(B) - row_off(A) : 0) + 16*sub:
     // the difference is masked per lane (hmask = ~0 in lanes 32-63), so a row pair costs
     // two v_and and two 64-bit adds — no 64-bit selects between scalar operands
@@ -437,7 +376,7 @@ __device__ __forceinline__ bool load_add_s(uintptr_t tb, uint32_t ldb, uint32_t 
         dd[u] = row_off_s(ib[u], ldb, nrows, bad) - oa[u];
     }
     if (bad) return false;
-    V buf[UU];
+    u32x4 buf[UU];
 #pragma unroll
     for (int u = 0; u < UU; ++u) {
         const uint64_t a = ((dd[u] & hmask) + lane_off) + (tb + oa[u]);
@@ -450,16 +389,7 @@ __device__ __forceinline__ bool load_add_s(uintptr_t tb, uint32_t ldb, uint32_t 
 #pragma unroll
     for (int u = 0; u < UU; ++u) {
         T x[N];
-        __builtin_memcpy(x, &buf[u], BPL);
-        if constexpr (NA != 0) {
-            if (u == 0 && first_batch) {
-#pragma unroll
-                for (int k = 0; k < N; ++k) acc[k] = A(x[k]);
-            } else {
-                asm volatile("" ::"v"(buf[u]));
-            }
-            continue;
-        }
+        __builtin_memcpy(x, &buf[u], 16);
 #pragma unroll
         for (int k = 0; k < N; ++k) {
             if (u == 0)
@@ -473,42 +403,39 @@ __device__ __forceinline__ bool load_add_s(uintptr_t tb, uint32_t ldb, uint32_t 
 
 // The bag pair again, one row at a time with per-lane range checks: an out-of-range
 // index contributes a zero row and is counted (the reference leaves it undefined).
-template <typename T, typename A, int BPL = 16>
+template <typename T, typename A>
 __device__ __forceinline__ void bag_pair_checked(uintptr_t tb, uint32_t ldb, uint32_t nrows,
                                                  const int64_t* ia, const int64_t* ib, bool hi,
                                                  int sub, int pool, A* acc, int* bad) {
-    constexpr int N = BPL / (int)sizeof(T);
-    typedef typename SgVec<BPL>::type V;
+    constexpr int N = 16 / (int)sizeof(T);
     const int64_t* ip = hi ? ib : ia;
 #pragma unroll 1
     for (int i = 0; i < pool; ++i) {
         const uint64_t r = (uint64_t)(ip[i] - 1);
         const bool ok = r < (uint64_t)nrows;
         *bad += ok ? 0 : 1;
-        const V v = *(reinterpret_cast<const V*>(
-                          tb + (uint64_t)(ok ? (uint32_t)r : 0u) * ldb) + sub);
+        const u32x4 v = *(reinterpret_cast<const u32x4*>(
+                              tb + (uint64_t)(ok ? (uint32_t)r : 0u) * ldb) + sub);
         T x[N];
-        const V z = ok ? v : V(0u);
-        __builtin_memcpy(x, &z, BPL);
+        unpack16<T, N>(ok ? v : u32x4{0u, 0u, 0u, 0u}, x);
         for (int k = 0; k < N; ++k) acc[k] = i == 0 ? A(x[k]) : A(acc[k] + A(x[k]));
     }
 }
 
 // `rounds` rounds of 8 bags per workgroup (bag mapping identical to run_bags: wave w
 // of round r holds bags chunk*8*rounds + r*8 + 2w + {0, 1}).
-template <typename T, typename A, int U, bool NT, bool NTL, int BPL = 16, int NA = 0>
+template <typename T, typename A, int U, bool NT, bool NTL>
 __device__ __forceinline__ void run_bags_s(const et_lookup_desc& d, int64_t batch,
                                            T* __restrict__ dst, int64_t ld_dst, int64_t chunk,
                                            int rounds) {
-    constexpr int N = BPL / (int)sizeof(T);
-    typedef typename SgVec<BPL>::type V;
+    constexpr int N = 16 / (int)sizeof(T);
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const bool hi = lane >= 32;
     const int sub = lane & 31;
     uint32_t hm = hi ? ~0u : 0u;
     asm volatile("" : "+v"(hm));  // opaque: keep `dd & hmask` two v_and, not selects
-    const uint64_t hmask = ((uint64_t)hm << 32) | hm, lane_off = (uint64_t)sub * (uint64_t)BPL;
+    const uint64_t hmask = ((uint64_t)hm << 32) | hm, lane_off = (uint64_t)sub * 16u;
     const uintptr_t tb = reinterpret_cast<uintptr_t>(d.table);
     const uint32_t ldb = (uint32_t)(d.ld_table * (int64_t)sizeof(T)), nr = (uint32_t)d.nrows;
     const int pool = d.pool;
@@ -524,7 +451,7 @@ __device__ __forceinline__ void run_bags_s(const et_lookup_desc& d, int64_t batc
         bool ok = true;
         int i0 = 0;
 #define ET_LOAD_ADD_S(UU) \
-    load_add_s<T, A, UU, NTL, BPL, NA>(tb, ldb, nr, ia + i0, ib + i0, hmask, lane_off, i0 == 0, acc)
+    load_add_s<T, A, UU, NTL>(tb, ldb, nr, ia + i0, ib + i0, hmask, lane_off, i0 == 0, acc)
         for (; ok && i0 + U <= pool; i0 += U) ok = ET_LOAD_ADD_S(U);
         if constexpr (U > 4) {
             if (ok && pool - i0 >= 4) {
@@ -542,7 +469,7 @@ __device__ __forceinline__ void run_bags_s(const et_lookup_desc& d, int64_t batc
 #undef ET_LOAD_ADD_S
         int bad = 0;
         if (!ok)
-            bag_pair_checked<T, A, BPL>(tb, ldb, nr, d.idx + bag * d.ld_idx,
+            bag_pair_checked<T, A>(tb, ldb, nr, d.idx + bag * d.ld_idx,
                                    d.idx + (has_b ? bag + 1 : bag) * d.ld_idx, hi, sub, pool, acc,
                                    &bad);
         if (hi && !has_b) bad = 0;  // the upper half re-ran bag A: counted by the lower
@@ -551,10 +478,9 @@ __device__ __forceinline__ void run_bags_s(const et_lookup_desc& d, int64_t batc
             T y[N];
 #pragma unroll
             for (int k = 0; k < N; ++k) y[k] = T(acc[k]);
-            V* o = reinterpret_cast<V*>(dst + (bag + (hi ? 1 : 0)) * ld_dst + d.dst_row_off) + sub;
-            V yv;
-            __builtin_memcpy(&yv, y, BPL);
-            store_v<NT>(o, yv);
+            u32x4* o =
+                reinterpret_cast<u32x4*>(dst + (bag + (hi ? 1 : 0)) * ld_dst + d.dst_row_off) + sub;
+            store16<NT>(o, pack16<T, N>(y));
         }
     }
 }
@@ -570,10 +496,9 @@ __global__ __launch_bounds__(256) void k_pooled_vec(LookupPack pack, int ntables
     const int t = (int)(item % ntables);
     const int64_t chunk = item / ntables;
     if constexpr (SG)
-        run_bags_s<T, A, U, NT, false, sg_bpl<T>(D)>(pack.d[t], batch, dst, ld_dst, chunk, rounds);
+        run_bags_s<T, A, U, NT, false>(pack.d[t], batch, dst, ld_dst, chunk, rounds);
     else
-        run_bags<T, A, D, U, NT, false, false, PG, MK>(pack.d[t], batch, dst, ld_dst, chunk,
-                                                       rounds);
+        run_bags<T, A, D, U, NT, false, PG, MK>(pack.d[t], batch, dst, ld_dst, chunk, rounds);
 }
 
 // XCD-aware stripe schedule for multi-table launches.  Every table's chunks are cut
@@ -590,25 +515,19 @@ constexpr int kXcds = 8;
 // has no scalar byte loads).
 constexpr int kMaxStripeEntries = 40;  // per XCD (kernel-argument size bound)
 struct StripeMap {
-    // entry[x][k]: table (bits 0-7), stripe (8-15), feature group + 1 (16-23; 0: whole
-    // rows); every XCD has nent entries (the feature-split tables take fsplit_g each)
+    // entry[x][k]: table (bits 0-7), stripe (8-15); every XCD has one entry per table
     uint32_t entry[kXcds][kMaxStripeEntries];
     int nent;
-    int fsplit_g;          // feature groups of a split table (2, 4 or 8)
     uint32_t ntload_mask;  // bit t: non-temporal row loads for table t
     uint32_t prio_mask;    // bit t: table t's waves run at raised issue priority
-    int prio;
     int nheavy;            // entry[x][0, nheavy): the heavy tables (> light_bytes)
-    int qorder;            // queued schedule: 1 = every heavy item before the light ones
     // queued schedule, class preference of a workgroup (k_pooled_vec_queued): 0 = none (one
-    // queue per XCD), 1 = policy A (fab_share sixteenths of the CUs prefer the fabric class),
-    // 2 = policy B (at most cache_cap cache workgroups resident per XCD)
+    // queue per XCD), 1 = policy A (fab_share sixteenths of the CUs prefer the fabric class)
     int affinity;
     int fab_share;
-    int cache_cap;
 };
 
-template <typename T, typename A, int D, int U, bool NT, bool NTI, bool SG = false, int NA = 0>
+template <typename T, typename A, int D, int U, bool NT, bool SG>
 __device__ __forceinline__ void striped_body(const LookupPack& pack, const StripeMap& sm,
                                              int ntables, int64_t batch, T* __restrict__ dst,
                                              int64_t ld_dst, int rounds, int64_t stripe_chunks,
@@ -621,71 +540,41 @@ __device__ __forceinline__ void striped_body(const LookupPack& pack, const Strip
     const int64_t chunk = (int64_t)((e >> 8) & 0xff) * stripe_chunks + j;
     if (j >= stripe_chunks || chunk >= nchunks) return;
     if ((sm.prio_mask >> t) & 1u) __builtin_amdgcn_s_setprio(2);
-#ifdef ET_FSPLIT
-    // Feature-split tables (experiment build only, -DET_FSPLIT: measured slower, and the
-    // slice loop's registers cost the default kernel 1.6% of the headline when compiled in)
-    if constexpr (D == 128 && sizeof(T) == 4) {
-        const uint32_t fg = e >> 16;
-        if (fg != 0u) {  // a feature slice of a split table (build_stripe_map)
-            if constexpr (SG) {
-                // G = 2: 256-byte half rows through the scalar-addressed loop with 8-byte lanes
-                // (round 4's 256-byte row loop, run_bags_s BPL = 8): the table and output
-                // columns start fofs features on, the row stride is the table's
-                if (sm.fsplit_g == 2) {
-                    et_lookup_desc h = pack.d[t];
-                    const int fofs = (int)(fg - 1u) * (D / 2);
-                    h.table = reinterpret_cast<const T*>(h.table) + fofs;
-                    h.dst_row_off += fofs;
-                    run_bags_s<T, A, U, NT, false, 8>(h, batch, dst, ld_dst, chunk, rounds);
-                    return;
-                }
-            }
-            const int64_t per_round = SG ? 8 : 4 * VecGeom<T, D>::GPW;
-            const int64_t b0 = chunk * per_round * rounds, b1 = b0 + per_round * rounds;
-            const int fofs = (int)(fg - 1u) * (D / sm.fsplit_g);
-            switch (sm.fsplit_g) {
-                case 2: run_bags_slice<T, A, D / 2, NT>(pack.d[t], batch, dst, ld_dst, b0, b1, fofs); break;
-                case 8: run_bags_slice<T, A, D / 8, NT>(pack.d[t], batch, dst, ld_dst, b0, b1, fofs); break;
-                default: run_bags_slice<T, A, D / 4, NT>(pack.d[t], batch, dst, ld_dst, b0, b1, fofs); break;
-            }
-            return;
-        }
-    }
-#endif
     if constexpr (SG) {
         if ((sm.ntload_mask >> t) & 1u)
-            run_bags_s<T, A, U, NT, true, sg_bpl<T>(D), NA>(pack.d[t], batch, dst, ld_dst, chunk,
-                                                             rounds);
+            run_bags_s<T, A, U, NT, true>(pack.d[t], batch, dst, ld_dst, chunk, rounds);
         else
-            run_bags_s<T, A, U, NT, false, sg_bpl<T>(D), NA>(pack.d[t], batch, dst, ld_dst, chunk,
-                                                              rounds);
+            run_bags_s<T, A, U, NT, false>(pack.d[t], batch, dst, ld_dst, chunk, rounds);
     } else {
         if ((sm.ntload_mask >> t) & 1u)
-            run_bags<T, A, D, U, NT, true, NTI>(pack.d[t], batch, dst, ld_dst, chunk, rounds);
+            run_bags<T, A, D, U, NT, true>(pack.d[t], batch, dst, ld_dst, chunk, rounds);
         else
-            run_bags<T, A, D, U, NT, false, NTI>(pack.d[t], batch, dst, ld_dst, chunk, rounds);
+            run_bags<T, A, D, U, NT, false>(pack.d[t], batch, dst, ld_dst, chunk, rounds);
     }
 }
 
+// Profiling build only (-DET_WG_TIMELINE, tools/wg_timeline.sh; never in the library the
+// package loads): every workgroup of a striped or queued launch records its start / end on the
+// 100 MHz constant clock, its table, its item's home XCD, the XCC it ran on and its hardware
+// slot, read back by et_debug_timeline.  Otherwise both calls compile to nothing.
 #ifdef ET_WG_TIMELINE
-// Profiling build only (tools/wg_timeline.sh; never in the library the package loads):
-// every workgroup of the striped launch records its start / end on the 100 MHz
-// constant clock, its table, XCC and hardware slot, read back by et_debug_timeline.
 constexpr uint32_t kTlCap = 1u << 17;
 __device__ uint4 g_tl[kTlCap][2];
 #endif
 
-template <typename T, typename A, int D, int U, bool NT, bool NTI = false, bool SG = false>
-__global__ __launch_bounds__(256) void k_pooled_vec_striped(LookupPack pack, StripeMap sm,
-                                                            int ntables, int64_t batch,
-                                                            T* __restrict__ dst, int64_t ld_dst,
-                                                            int rounds, int64_t stripe_chunks,
-                                                            int64_t nchunks) {
+__device__ __forceinline__ uint64_t tl_begin() {
 #ifdef ET_WG_TIMELINE
-    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    return __builtin_amdgcn_s_memrealtime();
+#else
+    return 0;
 #endif
-    striped_body<T, A, D, U, NT, NTI, SG>(pack, sm, ntables, batch, dst, ld_dst, rounds,
-                                          stripe_chunks, nchunks);
+}
+
+// The stamp of the workgroup that ran slot `slot` of XCD x's stripes (x < 0: it found no item).
+// Word 4 is table | x << 8, the table 0xff for an empty slot.
+__device__ __forceinline__ void tl_stamp(uint64_t t0, const StripeMap& sm, int ntables,
+                                         int64_t stripe_chunks, int64_t nchunks, int x,
+                                         int64_t slot) {
 #ifdef ET_WG_TIMELINE
     __syncthreads();
     if (threadIdx.x == 0 && blockIdx.x < kTlCap) {
@@ -693,17 +582,30 @@ __global__ __launch_bounds__(256) void k_pooled_vec_striped(LookupPack pack, Str
         uint32_t xcc, hw;
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        const int x = blockIdx.x % kXcds;
-        const int64_t slot = blockIdx.x / kXcds;
-        const int64_t j = slot / ntables;
-        const uint32_t e = sm.entry[x][slot % ntables];
-        const int64_t chunk = (int64_t)(e >> 8) * stripe_chunks + j;
-        const uint32_t t = j >= stripe_chunks || chunk >= nchunks ? 0xffu : (e & 0xffu);
+        uint32_t t = 0xffu;
+        if (x >= 0) {
+            const int64_t j = slot / ntables;
+            const uint32_t e = sm.entry[x][slot % ntables];
+            const int64_t chunk = (int64_t)((e >> 8) & 0xff) * stripe_chunks + j;
+            t = (j >= stripe_chunks || chunk >= nchunks ? 0xffu : (e & 0xffu)) | ((uint32_t)x << 8);
+        }
         g_tl[blockIdx.x][0] = make_uint4((uint32_t)t0, (uint32_t)(t0 >> 32), (uint32_t)t1,
                                          (uint32_t)(t1 >> 32));
         g_tl[blockIdx.x][1] = make_uint4(t, xcc, hw, gridDim.x);
     }
 #endif
+}
+
+template <typename T, typename A, int D, int U, bool NT, bool SG = false>
+__global__ __launch_bounds__(256) void k_pooled_vec_striped(LookupPack pack, StripeMap sm,
+                                                            int ntables, int64_t batch,
+                                                            T* __restrict__ dst, int64_t ld_dst,
+                                                            int rounds, int64_t stripe_chunks,
+                                                            int64_t nchunks) {
+    const uint64_t t0 = tl_begin();
+    striped_body<T, A, D, U, NT, SG>(pack, sm, ntables, batch, dst, ld_dst, rounds, stripe_chunks,
+                                     nchunks);
+    tl_stamp(t0, sm, ntables, stripe_chunks, nchunks, blockIdx.x % kXcds, blockIdx.x / kXcds);
 }
 
 // Per-XCD work queues: the same stripe map, but a workgroup takes its
@@ -741,15 +643,11 @@ __global__ __launch_bounds__(256) void k_pooled_vec_striped(LookupPack pack, Str
 //     with no fabric-class neighbour a light workgroup lasts 42 us instead of 57 (a light
 //     workgroup's L2 hits return no sooner than the fabric round trips queued ahead of them on
 //     a shared CU); headline 1.212 vs 1.226 ms for the parent, shares 6 / 7 / 9 / 10 / 12 at
-//     1.26 / 1.22 / 1.24 / 1.33 / 1.73 (profiles/r07/cu_affinity/, DESIGN §4 "CU affinity");
-//   policy B (experiment builds, ET_AFFINITY=B): a workgroup prefers the cache class while
-//     fewer than cache_cap cache workgroups are resident on its XCD (resident[x], counted at
-//     the claim, released by thread 0 when the cache item ends) — 2.1-2.5 ms, dropped.
+//     1.26 / 1.22 / 1.24 / 1.33 / 1.73 (profiles/r07/cu_affinity/, DESIGN §4 "CU affinity").
 struct XcdQueue {
     uint32_t head[kXcds][2];    // [x][0]: fabric class (or the whole queue); [x][1]: cache class
     uint32_t done;
-    uint32_t resident[kXcds];   // policy B: cache workgroups running on XCD x
-    uint32_t pad[32 - 3 * kXcds - 1];  // one 128-byte line
+    uint32_t pad[32 - 2 * kXcds - 1];  // one 128-byte line, all of it zeroed by the reset
 };
 static_assert(sizeof(XcdQueue) == ET_LOOKUP_QUEUE_BYTES, "queue block size (include/embtab.h)");
 
@@ -785,15 +683,13 @@ __device__ __forceinline__ uint32_t claim_pref(XcdQueue& q, uint32_t x0, uint32_
     return it;
 }
 
-template <typename T, typename A, int D, int U, bool NT, bool SG, int NA = 0>
+template <typename T, typename A, int D, int U, bool NT, bool SG>
 __global__ __launch_bounds__(256) void k_pooled_vec_queued(LookupPack pack, StripeMap sm,
                                                            int ntables, int64_t batch,
                                                            T* __restrict__ dst, int64_t ld_dst,
                                                            int rounds, int64_t stripe_chunks,
                                                            int64_t nchunks) {
-#ifdef ET_WG_TIMELINE
-    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    const uint64_t t0 = tl_begin();
     __shared__ uint32_t s_item;
     XcdQueue& q = *pack.queue;
     const uint32_t per = (uint32_t)(ntables * stripe_chunks);  // items per XCD
@@ -806,24 +702,8 @@ __global__ __launch_bounds__(256) void k_pooled_vec_queued(LookupPack pack, Stri
             const uint32_t nh = (uint32_t)sm.nheavy, sc = (uint32_t)stripe_chunks;
             uint32_t hw;
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-            uint32_t p = cu_hash16(hw) < (uint32_t)sm.fab_share ? 0u : 1u;  // policy A
-#ifdef ET_EXPERIMENTS
-            uint32_t counted = 0u;
-            if (sm.affinity == 2) {  // policy B
-                counted = atomicAdd(&q.resident[x0], 1u) < (uint32_t)sm.cache_cap ? 1u : 0u;
-                if (!counted) atomicSub(&q.resident[x0], 1u);
-                p = counted;
-            }
-#endif
+            const uint32_t p = cu_hash16(hw) < (uint32_t)sm.fab_share ? 0u : 1u;  // policy A
             it = claim_pref(q, x0, p, nh, (uint32_t)ntables, sc);
-#ifdef ET_EXPERIMENTS
-            if (sm.affinity == 2) {
-                // resident[x0] counts the workgroups that run a cache item on x0
-                const bool cache = it != ~0u && (it % per) % (uint32_t)ntables >= nh;
-                if (cache && !counted) atomicAdd(&q.resident[x0], 1u);
-                if (!cache && counted) atomicSub(&q.resident[x0], 1u);
-            }
-#endif
         } else
         for (uint32_t k = 0; k < (uint32_t)kXcds; ++k) {
             const uint32_t x = (xcc + k) & (uint32_t)(kXcds - 1);
@@ -837,75 +717,18 @@ __global__ __launch_bounds__(256) void k_pooled_vec_queued(LookupPack pack, Stri
     }
     __syncthreads();
     const uint32_t it = s_item;
-    if (it != ~0u) {
-        int64_t slot = (int64_t)(it % per);
-#ifdef ET_EXPERIMENTS
-        if (sm.affinity != 0) {
-            // the class queues keep the static order within each class (claim_class)
-        } else if (sm.qorder == 1 && sm.nheavy > 0 && sm.nheavy < ntables) {
-            // heavy-first: the queue's first nheavy * stripe_chunks items are the heavy
-            // tables' chunks, then the light ones (slot = j * ntables + k, as the static order)
-            const int64_t hn = (int64_t)sm.nheavy * stripe_chunks;
-            const int nl = ntables - sm.nheavy;
-            slot = slot < hn ? (slot / sm.nheavy) * ntables + slot % sm.nheavy
-                             : ((slot - hn) / nl) * ntables + sm.nheavy + (slot - hn) % nl;
-        } else if (sm.qorder == 2 && sm.nheavy > 0 && sm.nheavy < ntables) {  // light first
-            const int nl = ntables - sm.nheavy;
-            const int64_t ln = (int64_t)nl * stripe_chunks;
-            slot = slot < ln ? (slot / nl) * ntables + sm.nheavy + slot % nl
-                             : ((slot - ln) / sm.nheavy) * ntables + (slot - ln) % sm.nheavy;
-        }
-#endif
-        striped_body<T, A, D, U, NT, false, SG, NA>(pack, sm, ntables, batch, dst, ld_dst, rounds,
-                                                    stripe_chunks, nchunks, (int)(it / per), slot);
-    }
-#ifdef ET_WG_TIMELINE
-    // Profiling build only (tools/wg_timeline.sh): the stamps of k_pooled_vec_striped, with the
-    // claimed item's table and home XCD
-    __syncthreads();
-    if (threadIdx.x == 0 && blockIdx.x < kTlCap) {
-        const uint64_t t1 = __builtin_amdgcn_s_memrealtime();
-        uint32_t xcc, hw;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        uint32_t t = 0xffu;
-        if (it != ~0u) {
-            const int64_t slot = (int64_t)(it % per);
-            const uint32_t e = sm.entry[it / per][slot % ntables];
-            const int64_t chunk = (int64_t)((e >> 8) & 0xff) * stripe_chunks + slot / ntables;
-            t = (chunk >= nchunks ? 0xffu : (e & 0xffu)) | ((it / per) << 8);
-        }
-        g_tl[blockIdx.x][0] = make_uint4((uint32_t)t0, (uint32_t)(t0 >> 32), (uint32_t)t1,
-                                         (uint32_t)(t1 >> 32));
-        g_tl[blockIdx.x][1] = make_uint4(t, xcc, hw, gridDim.x);
-    }
-#endif
-#ifdef ET_EXPERIMENTS
-    if (threadIdx.x == 0 && sm.affinity == 2 && it != ~0u &&
-        (it % per) % (uint32_t)ntables >= (uint32_t)sm.nheavy) {
-        uint32_t xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        atomicSub(&q.resident[xcc & (uint32_t)(kXcds - 1)], 1u);
-        __threadfence();  // the release lands before this workgroup counts as done (the reset)
-    }
-#endif
+    // the class queues keep the static order within each class (claim_class)
+    if (it != ~0u)
+        striped_body<T, A, D, U, NT, SG>(pack, sm, ntables, batch, dst, ld_dst, rounds,
+                                         stripe_chunks, nchunks, (int)(it / per),
+                                         (int64_t)(it % per));
+    tl_stamp(t0, sm, ntables, stripe_chunks, nchunks, it != ~0u ? (int)(it / per) : -1,
+             (int64_t)(it % per));
     if (threadIdx.x == 0 && atomicAdd(&q.done, 1u) == gridDim.x - 1u) {  // the last one
         uint32_t* w = reinterpret_cast<uint32_t*>(&q);
         for (int i = 0; i < (int)(sizeof(XcdQueue) / sizeof(uint32_t)); ++i) atomicExch(&w[i], 0u);
     }
 }
-
-#ifdef ET_EXPERIMENTS
-// The same kernel held to 64 VGPRs (8 waves per SIMD instead of 7): ET_W8=1 experiment.
-template <typename T, typename A, int D, int U, bool NT, bool NTI = false, bool SG = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void
-k_pooled_vec_striped_w8(LookupPack pack, StripeMap sm, int ntables, int64_t batch,
-                        T* __restrict__ dst, int64_t ld_dst, int rounds, int64_t stripe_chunks,
-                        int64_t nchunks) {
-    striped_body<T, A, D, U, NT, NTI, SG>(pack, sm, ntables, batch, dst, ld_dst, rounds,
-                                          stripe_chunks, nchunks);
-}
-#endif
 
 // Non-reducing gather (bit copy) of RB-byte rows: each group moves U rows at once.
 template <int RB, bool NT>
@@ -970,9 +793,10 @@ __global__ __launch_bounds__(256) void k_gather_vec(LookupPack pack, int ntables
 // (RB / 16 lanes, one 16-byte vector each) holding its U rows in flight at once and storing each
 // as it arrives (vector loads return in order, so the store of row u waits for rows 0..u only).
 // U = 8, W = 4 — 1,024 workgroups at B = 65,536 — measured 14.32-14.40 us per graph-replayed
-// launch against 15.25 for round 5's k_gather_pipe (two rounds of 8 in 512 workgroups), U = 16
-// 15.6-15.8, U = 4 / W = 8 14.9, U = 6 / 12 15.6-15.9, W = 2 / 8 / 1 14.48-14.58 / 14.40-14.43 /
-// 14.87 (profiles/r06/cfg2_variants.txt; ET_GATHER_ONE / ET_GATHER_W in experiment builds).
+// launch against 15.25 for round 5's two-round pipelined gather (two rounds of 8 in 512
+// workgroups), U = 16 15.6-15.8, U = 4 / W = 8 14.9, U = 6 / 12 15.6-15.9, W = 2 / 8 / 1
+// 14.48-14.58 / 14.40-14.43 / 14.87 (profiles/r06/cfg2_variants.txt); the host launches U = 8,
+// W = 4 only.
 template <int RB, bool NT, bool NTL, int U, int W = 4>
 __global__ __launch_bounds__(64 * W) void k_gather_one(LookupPack pack, int ntables, int64_t batch,
                                                        char* __restrict__ dst, int64_t ld_dst_b,
@@ -1041,151 +865,6 @@ __global__ __launch_bounds__(64 * W) void k_gather_one(LookupPack pack, int ntab
     }
 #endif
 }
-
-#ifdef ET_EXPERIMENTS
-// Experiment (ET_GATHER_S=1, config 2): 512-byte rows with the indices read through the SCALAR
-// cache — each wave's 16 contiguous bags' indices by scalar loads (vector indices, ld_idx = 1),
-// so the index reads do not queue behind the row reads in the CU's vector memory path (the
-// gather timeline shows wave 0's index loads returning after 1-8 us) — then k_gather_one's
-// round: 8 rows per half-wave in flight, each stored as it arrives.
-template <bool NT, bool NTL>
-__global__ __launch_bounds__(256) void k_gather_s512(LookupPack pack, int ntables, int64_t batch,
-                                                     char* __restrict__ dst, int64_t ld_dst_b,
-                                                     int es) {
-    const int64_t item = blockIdx.x;
-    const int t = (int)(item % ntables);
-    const int64_t chunk = item / ntables;
-    const et_lookup_desc& d = pack.d[t];
-    const char* table = reinterpret_cast<const char*>(d.table);
-    const uint64_t ld_b = (uint64_t)(d.ld_table * es);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int hi = lane >= 32 ? 1 : 0;
-    const int sub = lane & 31;
-    const int64_t base = chunk * 64 + wave * 16;
-    if (base >= batch) return;  // wave-uniform
-    const cidx_ptr ip = as_scalar_idx(d.idx + base);
-    int64_t iv[16];
-    if (base + 16 <= batch) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) iv[k] = ip[k];
-    } else {
-        const int64_t last = batch - 1 - base;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) iv[k] = ip[k < last ? k : last];
-    }
-    u32x4 cur[8];
-    bool ok[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const uint64_t row = (uint64_t)((hi ? iv[2 * u + 1] : iv[2 * u]) - 1);
-        ok[u] = row < (uint64_t)d.nrows;
-        const u32x4* src = reinterpret_cast<const u32x4*>(table + (ok[u] ? row * ld_b : 0)) + sub;
-        if constexpr (NTL) cur[u] = __builtin_nontemporal_load(src);
-        else cur[u] = *src;
-    }
-    int bad = 0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int64_t bag = base + 2 * u + hi;
-        if (bag < batch) {
-            bad += ok[u] ? 0 : 1;
-            u32x4* o = reinterpret_cast<u32x4*>(dst + bag * ld_dst_b + d.dst_row_off * es) + sub;
-            store16<NT>(o, ok[u] ? cur[u] : u32x4{0u, 0u, 0u, 0u});
-        }
-    }
-    if (bad && sub == 0) note_oob(bad);
-}
-#endif
-
-#ifdef ET_EXPERIMENTS
-// The same gather, software-pipelined over `rounds` rounds per workgroup: round r + 1's rows
-// are loaded before round r's are stored, and round r + 2's indices before those, so each
-// wave keeps a round of rows in flight while it writes the previous one.  The one-round
-// kernel loads every row of the launch, then stores them all: reads and writes never overlap
-// (config 2: 18.5 us per kernel for 67.6 MB, compulsory traffic only by PMC; pipelined: 15.5,
-// profiles/r05/cfg2/).  Vector memory counters retire in issue order, so the issue order is
-// indices(r + 2), store(r), rows(r + 1): the store waits only for round r's rows, the row
-// addresses of round r + 1 only for indices issued before them.  Rows of 16 * LPR bytes, one
-// vector per lane (NV = 1).  Bit copies, so any schedule gives the same bytes.
-template <int RB, bool NT, bool NTL = false>
-__global__ __launch_bounds__(256) void k_gather_pipe(LookupPack pack, int ntables, int64_t batch,
-                                                     char* __restrict__ dst, int64_t ld_dst_b,
-                                                     int es, int rounds) {
-    constexpr int VPR = RB / 16;
-    static_assert(VPR <= 64 && 64 % VPR == 0, "one vector per lane");
-    constexpr int LPR = VPR;
-    constexpr int GPW = 64 / LPR;
-    constexpr int U = 8;
-    const int64_t item = blockIdx.x;
-    const int t = (int)(item % ntables);
-    const int64_t chunk = item / ntables;
-    const et_lookup_desc& d = pack.d[t];
-    const char* table = reinterpret_cast<const char*>(d.table);
-    const int64_t ld_b = d.ld_table * es;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane / LPR, sub = lane % LPR;
-    const int64_t per_round = 4 * GPW;
-    const int64_t step = per_round * U;  // bags per round
-    const int64_t bag_base = chunk * step * rounds + wave * GPW + g;
-    auto bag_of = [&](int r, int u) { return bag_base + r * step + u * per_round; };
-    auto idx_of = [&](int r, int u) {
-        int64_t b = bag_of(r, u);
-        b = b < batch ? b : batch - 1;  // keep every lane active
-        return d.idx[b * d.ld_idx];
-    };
-    int64_t iv[U];    // indices of round r + 1 (then r + 2)
-    u32x4 cur[U];     // rows of round r
-    bool okc[U];
-    int bad = 0;
-    // prologue: round 0's indices and rows, round 1's indices
-#pragma unroll
-    for (int u = 0; u < U; ++u) iv[u] = idx_of(0, u);
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const uint64_t row = (uint64_t)(iv[u] - 1);
-        okc[u] = row < (uint64_t)d.nrows;
-        const u32x4* src = reinterpret_cast<const u32x4*>(table + (okc[u] ? row * (uint64_t)ld_b : 0)) + sub;
-        if constexpr (NTL) cur[u] = __builtin_nontemporal_load(src);
-        else cur[u] = *src;
-    }
-    if (rounds > 1)
-#pragma unroll
-        for (int u = 0; u < U; ++u) iv[u] = idx_of(1, u);
-    for (int r = 0; r < rounds; ++r) {
-        if (bag_of(r, 0) >= batch) break;  // uniform per group: later rounds are past too
-        int64_t nx[U];
-        if (r + 2 < rounds)
-#pragma unroll
-            for (int u = 0; u < U; ++u) nx[u] = idx_of(r + 2, u);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int64_t bag = bag_of(r, u);
-            if (bag < batch) {
-                bad += okc[u] ? 0 : 1;
-                u32x4* o = reinterpret_cast<u32x4*>(dst + bag * ld_dst_b + d.dst_row_off * es) + sub;
-                store16<NT>(o, okc[u] ? cur[u] : u32x4{0u, 0u, 0u, 0u});
-            }
-        }
-        if (r + 1 < rounds) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint64_t row = (uint64_t)(iv[u] - 1);
-                okc[u] = row < (uint64_t)d.nrows;
-                const u32x4* src =
-                    reinterpret_cast<const u32x4*>(table + (okc[u] ? row * (uint64_t)ld_b : 0)) + sub;
-                if constexpr (NTL) cur[u] = __builtin_nontemporal_load(src);
-                else cur[u] = *src;
-            }
-        }
-        if (r + 2 < rounds)
-#pragma unroll
-            for (int u = 0; u < U; ++u) iv[u] = nx[u];
-    }
-    if (bad && sub == 0) note_oob(bad);
-}
-#endif  // ET_EXPERIMENTS: round 5's two-round gather (ET_GATHER_PIPE=2..)
-
 
 // Generic path: any feature size / alignment / per-table dims / paged tables.  One wave
 // per bag, lanes stride over the features, pool order sequential per feature.
@@ -1278,26 +957,15 @@ struct LookupTuning {
     // (measured -5% on the Criteo mix; nt on the cache-resident mid-size tables hurts).
     int ntload = 1;                          // ET_NTLOAD=0 disables
     int64_t ntload_bytes = 256ll << 20;      // ET_NTLOAD_BYTES
-    int ntidx = 0;                           // ET_NTIDX=1: non-temporal index loads
     int max_rounds = 8;                      // ET_ROUNDS: max bag rounds per workgroup
     int64_t light_bytes = 4 << 20; // tables up to one XCD L2 (4 MiB) are "light"
-    int rows_in_flight = 0;        // ET_U=4|8|16: rows per group in flight (fp32 D=128)
-    int w8 = 0;                    // ET_W8=1: the striped kernel held to 8 waves per SIMD
     int sgpr = 1;                  // ET_SGPR=0: 512-byte rows use the per-lane loop too
-    int sg256 = 0;                 // ET_SG256=1: 256-byte rows take the scalar loop too
     int heavy_prio = 0;            // ET_HEAVY_PRIO=1: heavy tables' waves at priority 2
-    int qorder = 0;                // ET_QORDER=1: queued schedule, heavy items first
-    int noadd = 0;                 // ET_HEAD_NOADD=1: the scalar loop without its adds
     // Class preference of the queued schedule's workgroups (k_pooled_vec_queued, "CU affinity"):
-    // ET_AFFINITY=0|A|B, ET_FAB_SHARE (policy A, sixteenths of the CUs that prefer the fabric
-    // class; 0 = no preference), ET_CACHE_CAP (policy B, cache workgroups resident per XCD)
+    // ET_AFFINITY=0|A, ET_FAB_SHARE (sixteenths of the CUs that prefer the fabric class; 0 = no
+    // preference)
     int affinity = 1;              // policy A
     int fab_share = 8;             // the sweep's choice (profiles/r07/cu_affinity/sweep.txt)
-    int cache_cap = 64;
-    // Tables of (light_bytes, fsplit_bytes] cut into fsplit_g feature groups, group g on XCDs
-    // [g * 8 / G, (g + 1) * 8 / G), so each XCD's L2 holds 1/G of the table (ET_FSPLIT_*)
-    int64_t fsplit_bytes = 0;
-    int fsplit_g = 4;
 };
 
 inline const LookupTuning& tuning() {
@@ -1310,24 +978,13 @@ inline const LookupTuning& tuning() {
         }
         v.ntload = (int)ET_KNOB("ET_NTLOAD", v.ntload);
         v.ntload_bytes = ET_KNOB("ET_NTLOAD_BYTES", v.ntload_bytes);
-        v.ntidx = (int)ET_KNOB("ET_NTIDX", v.ntidx);
         v.max_rounds = (int)ET_KNOB("ET_ROUNDS", v.max_rounds);
         if (v.max_rounds < 1) v.max_rounds = 1;
         v.light_bytes = ET_KNOB("ET_LIGHT_BYTES", v.light_bytes);
-        v.rows_in_flight = (int)ET_KNOB("ET_U", v.rows_in_flight);
-        v.w8 = (int)ET_KNOB("ET_W8", v.w8);
-        v.noadd = (int)ET_KNOB("ET_HEAD_NOADD", v.noadd);
         v.sgpr = (int)ET_KNOB("ET_SGPR", v.sgpr);
-        v.sg256 = (int)ET_KNOB("ET_SG256", v.sg256);
         v.heavy_prio = (int)ET_KNOB("ET_HEAVY_PRIO", v.heavy_prio);
-        v.qorder = (int)ET_KNOB("ET_QORDER", v.qorder);
-        if (const char* e = getenv("ET_AFFINITY"))
-            v.affinity = *e == 'A' ? 1 : *e == 'B' ? 2 : 0;
+        if (const char* e = getenv("ET_AFFINITY")) v.affinity = *e == 'A' ? 1 : 0;
         v.fab_share = (int)ET_KNOB("ET_FAB_SHARE", v.fab_share);
-        v.cache_cap = (int)ET_KNOB("ET_CACHE_CAP", v.cache_cap);
-        v.fsplit_bytes = ET_KNOB("ET_FSPLIT_BYTES", v.fsplit_bytes);
-        const int g = (int)ET_KNOB("ET_FSPLIT_G", 4);
-        v.fsplit_g = g == 2 || g == 8 ? g : 4;
 #endif
         return v;
     }();
@@ -1338,27 +995,16 @@ int max_rounds() { return tuning().max_rounds; }
 
 // Stripe assignment: heavy tables -> stripe x on XCD x; light tables' stripes laid out
 // table after table (alternating large and small tables) and cut into kXcds equal runs.
-inline void build_stripe_map(const LookupPack& pack, int n, int es, StripeMap& sm,
-                             bool can_split = false) {
+inline void build_stripe_map(const LookupPack& pack, int n, int es, StripeMap& sm) {
     const LookupTuning& tu = tuning();
     int heavy[ET_MAX_TABLES_PER_LAUNCH], light[ET_MAX_TABLES_PER_LAUNCH];
-    int split[ET_MAX_TABLES_PER_LAUNCH];
-    int nh = 0, nl = 0, nsp = 0;
+    int nh = 0, nl = 0;
     int64_t bytes[ET_MAX_TABLES_PER_LAUNCH];
     sm.ntload_mask = 0;
     sm.prio_mask = 0;
-    sm.qorder = tu.qorder;
-    sm.fsplit_g = tu.fsplit_g;
     for (int t = 0; t < n; ++t) {
         bytes[t] = pack.d[t].nrows * pack.d[t].ld_table * es;
-#ifndef ET_FSPLIT
-        can_split = false;  // the slice loop is not compiled in (striped_body)
-#endif
-        if (can_split && bytes[t] > tu.light_bytes && bytes[t] <= tu.fsplit_bytes &&
-            pack.d[t].cols_per_page == 0 && pack.d[t].dim == 128 &&
-            n + (nsp + 1) * (tu.fsplit_g - 1) <= kMaxStripeEntries) {
-            split[nsp++] = t;
-        } else if (bytes[t] > tu.light_bytes) {
+        if (bytes[t] > tu.light_bytes) {
             heavy[nh++] = t;
             if (tu.heavy_prio) sm.prio_mask |= 1u << t;
             if (tu.ntload && bytes[t] > tu.ntload_bytes) sm.ntload_mask |= 1u << t;
@@ -1379,154 +1025,74 @@ inline void build_stripe_map(const LookupPack& pack, int n, int es, StripeMap& s
     int cnt[kXcds] = {0};
     for (int x = 0; x < kXcds; ++x)
         for (int h = 0; h < nh; ++h) sm.entry[x][cnt[x]++] = (uint32_t)heavy[h] | ((uint32_t)x << 8);
-    // split tables: XCD x serves feature group g = x / P (P = 8 / G XCDs per group) over the
-    // stripes G * (x % P) .. G * (x % P) + G - 1, so every group covers all 8 stripes
-    const int G = sm.fsplit_g, P = kXcds / G;
-    for (int x = 0; x < kXcds; ++x)
-        for (int q = 0; q < nsp; ++q)
-            for (int m = 0; m < G; ++m)
-                sm.entry[x][cnt[x]++] = (uint32_t)split[q] |
-                                        ((uint32_t)(G * (x % P) + m) << 8) |
-                                        ((uint32_t)(x / P + 1) << 16);
-    sm.nheavy = nh + nsp * G;
+    sm.nheavy = nh;
     // linear list of light stripes (order[i], st), st < kXcds; XCD x takes [x*nl, (x+1)*nl)
     for (int q = 0; q < nl * kXcds; ++q) {
         const int x = q / (nl > 0 ? nl : 1);
         sm.entry[x][cnt[x]++] = (uint32_t)order[q / kXcds] | ((uint32_t)(q % kXcds) << 8);
     }
     sm.nent = cnt[0];
-    // a class preference needs both classes (and, policy A, a share to prefer by): otherwise
-    // none, the one-queue schedule
+    // a class preference needs both classes and a share to prefer by: otherwise none, the
+    // one-queue schedule
     sm.affinity = sm.nheavy > 0 && sm.nheavy < sm.nent ? tu.affinity : 0;
     sm.fab_share = tu.fab_share < 0 ? 0 : tu.fab_share > 16 ? 16 : tu.fab_share;
-    sm.cache_cap = tu.cache_cap < 0 ? 0 : tu.cache_cap;
-    if (sm.affinity == 1 && sm.fab_share == 0) sm.affinity = 0;
+    if (sm.fab_share == 0) sm.affinity = 0;
 }
 
-template <typename T, typename A, int D, int U, bool NT, bool PG = false, bool MK = false>
-int launch_pooled_vec_u(const LookupPack& pack, int n, int64_t batch, void* dst, int64_t ld_dst,
-                        hipStream_t s);
-
-template <typename T, typename A, int D, bool NT, bool PG = false>
+// One pooled launch: the schedule (per-XCD queues, static stripes or the linear grid) and the
+// bag loop (scalar-addressed or per-lane) are chosen once, and each kernel has one call site.
+template <typename T, typename A, int D, bool NT, bool PG = false, bool MK = false>
 int launch_pooled_vec(const LookupPack& pack, int n, int64_t batch, void* dst, int64_t ld_dst,
                       hipStream_t s) {
-    if constexpr (PG)  // paged tables: one schedule, the default rows in flight
-        return launch_pooled_vec_u<T, A, D, VecGeom<T, D>::U, NT, true>(pack, n, batch, dst,
-                                                                         ld_dst, s);
-#ifdef ET_EXPERIMENTS
-    if constexpr (D == 128 && __is_same(T, float)) {
-        switch (tuning().rows_in_flight) {
-            case 4: return launch_pooled_vec_u<T, A, D, 4, NT>(pack, n, batch, dst, ld_dst, s);
-            case 16: return launch_pooled_vec_u<T, A, D, 16, NT>(pack, n, batch, dst, ld_dst, s);
-            default: break;
-        }
-    }
-#endif
-    return launch_pooled_vec_u<T, A, D, VecGeom<T, D>::U, NT>(pack, n, batch, dst, ld_dst, s);
-}
-
-template <typename T, typename A, int D, int U, bool NT, bool PG, bool MK>
-int launch_pooled_vec_u(const LookupPack& pack, int n, int64_t batch, void* dst, int64_t ld_dst,
-                        hipStream_t s) {
     using G = VecGeom<T, D>;
-    // the scalar-addressed loop: 512-byte rows, and 256-byte rows with 8-byte lanes (ET_SG256)
-    constexpr bool kSG = !PG && !MK && (D * (int)sizeof(T) == 512 || D * (int)sizeof(T) == 256);
-    bool sg = kSG && tuning().sgpr &&
-              (D * (int)sizeof(T) == 512 || tuning().sg256);  // row strides must fit 32 bits
+    constexpr int U = G::U;
+    // the scalar-addressed loop: 512-byte rows only, contiguous tables, no masking
+    constexpr bool kSG = !PG && !MK && D * (int)sizeof(T) == 512;
+    bool sg = kSG && tuning().sgpr;  // and every row stride must fit 32 bits
     for (int t = 0; t < n && sg; ++t) sg = pack.d[t].ld_table * (int64_t)sizeof(T) < (1ll << 32);
     const int64_t per_round = sg ? 8 : 4 * G::GPW;  // the scalar loop: two bags per wave
     const int rounds = rounds_for(batch, per_round, n);
     const int64_t nchunks = (batch + per_round * rounds - 1) / (per_round * rounds);
     if (nchunks <= 0) return ET_OK;
-    if (!PG && !MK && n > 1 && tuning().striped) {
-        StripeMap sm;
-        build_stripe_map(pack, n, (int)sizeof(T), sm, D == 128 && sizeof(T) == 4);
-        const int ne = sm.nent;  // entries per XCD (n, plus fsplit_g - 1 per split table)
-        const int64_t stripe_chunks = (nchunks + kXcds - 1) / kXcds;
-        const int64_t grid = (int64_t)kXcds * ne * stripe_chunks;
-        if (grid > 0x7fffffffll) return fail(ET_ERR_ARG, "grid too large");
-        if (pack.queue && tuning().queued && grid < 0xffffffffll) {
-            if constexpr (kSG) {
-#ifdef ET_EXPERIMENTS
-                if (sg && tuning().noadd) {  // ET_HEAD_NOADD: the adds-free ceiling variant
-                    hipLaunchKernelGGL((k_pooled_vec_queued<T, A, D, U, NT, true, 1>),
-                                       dim3((unsigned)grid), dim3(256), 0, s, pack, sm, ne, batch,
-                                       reinterpret_cast<T*>(dst), ld_dst, rounds, stripe_chunks,
-                                       nchunks);
-                    ET_LAUNCH_CHECK("k_pooled_vec_queued<noadd>");
-                    return ET_OK;
-                }
-#endif
-                if (sg) {
-                    hipLaunchKernelGGL((k_pooled_vec_queued<T, A, D, U, NT, true>),
-                                       dim3((unsigned)grid), dim3(256), 0, s, pack, sm, ne, batch,
-                                       reinterpret_cast<T*>(dst), ld_dst, rounds, stripe_chunks,
-                                       nchunks);
-                    ET_LAUNCH_CHECK("k_pooled_vec_queued");
-                    return ET_OK;
-                }
-            }
-            hipLaunchKernelGGL((k_pooled_vec_queued<T, A, D, U, NT, false>), dim3((unsigned)grid),
-                               dim3(256), 0, s, pack, sm, ne, batch, reinterpret_cast<T*>(dst),
-                               ld_dst, rounds, stripe_chunks, nchunks);
-            ET_LAUNCH_CHECK("k_pooled_vec_queued");
-            return ET_OK;
-        }
-#ifdef ET_EXPERIMENTS
-        if constexpr (kSG) {
-            if (sg && tuning().w8) {
-                hipLaunchKernelGGL((k_pooled_vec_striped_w8<T, A, D, U, NT, false, true>),
-                                   dim3((unsigned)grid), dim3(256), 0, s, pack, sm, ne, batch,
-                                   reinterpret_cast<T*>(dst), ld_dst, rounds, stripe_chunks,
-                                   nchunks);
-                ET_LAUNCH_CHECK("k_pooled_vec_striped");
-                return ET_OK;
-            }
-        }
-#endif
-        if constexpr (kSG) {
-            if (sg) {
-                hipLaunchKernelGGL((k_pooled_vec_striped<T, A, D, U, NT, false, true>),
-                                   dim3((unsigned)grid), dim3(256), 0, s, pack, sm, ne, batch,
-                                   reinterpret_cast<T*>(dst), ld_dst, rounds, stripe_chunks,
-                                   nchunks);
-                ET_LAUNCH_CHECK("k_pooled_vec_striped");
-                return ET_OK;
-            }
-        }
-#ifdef ET_EXPERIMENTS
-        if (tuning().w8 && D == 128 && __is_same(T, float))
-            hipLaunchKernelGGL((k_pooled_vec_striped_w8<T, A, D, U, NT>), dim3((unsigned)grid),
-                               dim3(256), 0, s, pack, sm, ne, batch, reinterpret_cast<T*>(dst),
-                               ld_dst, rounds, stripe_chunks, nchunks);
-        else if (tuning().ntidx && D == 128 && __is_same(T, float))
-            hipLaunchKernelGGL((k_pooled_vec_striped<T, A, D, U, NT, true>), dim3((unsigned)grid),
-                               dim3(256), 0, s, pack, sm, ne, batch, reinterpret_cast<T*>(dst),
-                               ld_dst, rounds, stripe_chunks, nchunks);
-        else
-#endif
-            hipLaunchKernelGGL((k_pooled_vec_striped<T, A, D, U, NT>), dim3((unsigned)grid),
-                               dim3(256), 0, s, pack, sm, ne, batch, reinterpret_cast<T*>(dst),
-                               ld_dst, rounds, stripe_chunks, nchunks);
-        ET_LAUNCH_CHECK("k_pooled_vec_striped");
-        return ET_OK;
+    const bool striped = !PG && !MK && n > 1 && tuning().striped;
+    StripeMap sm;
+    int64_t stripe_chunks = 0, grid = nchunks * n;
+    if (striped) {
+        build_stripe_map(pack, n, (int)sizeof(T), sm);
+        stripe_chunks = (nchunks + kXcds - 1) / kXcds;
+        grid = (int64_t)kXcds * sm.nent * stripe_chunks;
     }
-    const int64_t grid = nchunks * n;
-    if (grid <= 0) return ET_OK;
     if (grid > 0x7fffffffll) return fail(ET_ERR_ARG, "grid too large");
-    if constexpr (kSG) {
-        if (sg) {
-            hipLaunchKernelGGL((k_pooled_vec<T, A, D, U, NT, false, false, true>),
-                               dim3((unsigned)grid), dim3(256), 0, s, pack, n, batch,
-                               reinterpret_cast<T*>(dst), ld_dst, rounds);
-            ET_LAUNCH_CHECK("k_pooled_vec");
-            return ET_OK;
+    const bool queued = striped && pack.queue && tuning().queued;
+    // `loop` is std::true_type for the scalar-addressed loop (instantiated for kSG only)
+    auto launch = [&](auto loop) -> int {
+        constexpr bool SG = decltype(loop)::value;
+        T* out = reinterpret_cast<T*>(dst);
+        if constexpr (!PG && !MK) {
+            if (queued) {
+                hipLaunchKernelGGL((k_pooled_vec_queued<T, A, D, U, NT, SG>), dim3((unsigned)grid),
+                                   dim3(256), 0, s, pack, sm, sm.nent, batch, out, ld_dst, rounds,
+                                   stripe_chunks, nchunks);
+                ET_LAUNCH_CHECK("k_pooled_vec_queued");
+                return ET_OK;
+            }
+            if (striped) {
+                hipLaunchKernelGGL((k_pooled_vec_striped<T, A, D, U, NT, SG>), dim3((unsigned)grid),
+                                   dim3(256), 0, s, pack, sm, sm.nent, batch, out, ld_dst, rounds,
+                                   stripe_chunks, nchunks);
+                ET_LAUNCH_CHECK("k_pooled_vec_striped");
+                return ET_OK;
+            }
         }
+        hipLaunchKernelGGL((k_pooled_vec<T, A, D, U, NT, PG, MK, SG>), dim3((unsigned)grid),
+                           dim3(256), 0, s, pack, n, batch, out, ld_dst, rounds);
+        ET_LAUNCH_CHECK("k_pooled_vec");
+        return ET_OK;
+    };
+    if constexpr (kSG) {
+        if (sg) return launch(std::true_type{});
     }
-    hipLaunchKernelGGL((k_pooled_vec<T, A, D, U, NT, PG, MK>), dim3((unsigned)grid), dim3(256), 0, s,
-                       pack, n, batch, reinterpret_cast<T*>(dst), ld_dst, rounds);
-    ET_LAUNCH_CHECK("k_pooled_vec");
-    return ET_OK;
+    return launch(std::false_type{});
 }
 
 template <int RB, bool NT>
@@ -1544,82 +1110,22 @@ int launch_gather_rb(const LookupPack& pack, int n, int64_t batch, void* dst, in
         bool ntl = tuning().ntload != 0;
         for (int t = 0; t < n && ntl; ++t)
             ntl = pack.d[t].nrows * pack.d[t].ld_table * es > tuning().ntload_bytes;
-        bool one = true;
-#ifdef ET_EXPERIMENTS
-        // ET_GATHER_PIPE=R (R >= 2): round 5's k_gather_pipe over R rounds; 1: k_gather_vec
-        const int pr = (int)ET_KNOB("ET_GATHER_PIPE", 0);
-        one = pr == 0;
-        const int64_t g = pr > 1 ? (batch + per_round * pr - 1) / (per_round * pr) * n : 0;
-        if (pr > 1 && g >= 1) {
-            if (g > 0x7fffffffll) return fail(ET_ERR_ARG, "grid too large");
-            if (ntl)
-                hipLaunchKernelGGL((k_gather_pipe<RB, NT, true>), dim3((unsigned)g), dim3(256), 0,
-                                   s, pack, n, batch, reinterpret_cast<char*>(dst), ld_dst * es,
-                                   es, pr);
-            else
-                hipLaunchKernelGGL((k_gather_pipe<RB, NT>), dim3((unsigned)g), dim3(256), 0, s,
-                                   pack, n, batch, reinterpret_cast<char*>(dst), ld_dst * es, es,
-                                   pr);
-            ET_LAUNCH_CHECK("k_gather_pipe");
-            return ET_OK;
-        }
-        if constexpr (RB == 512) {
-            bool contig = ET_KNOB("ET_GATHER_S", 0) != 0;
-            for (int t = 0; t < n && contig; ++t) contig = pack.d[t].ld_idx == 1;
-            if (contig) {
-                const int64_t gs = (batch + 63) / 64 * n;
-                if (ntl)
-                    hipLaunchKernelGGL((k_gather_s512<NT, true>), dim3((unsigned)gs), dim3(256), 0,
-                                       s, pack, n, batch, reinterpret_cast<char*>(dst),
-                                       ld_dst * es, es);
-                else
-                    hipLaunchKernelGGL((k_gather_s512<NT, false>), dim3((unsigned)gs), dim3(256),
-                                       0, s, pack, n, batch, reinterpret_cast<char*>(dst),
-                                       ld_dst * es, es);
-                ET_LAUNCH_CHECK("k_gather_s512");
-                return ET_OK;
-            }
-        }
-        if (const int uo = (int)ET_KNOB("ET_GATHER_ONE", 0)) {  // U / W variants of k_gather_one
-            const int w = (int)ET_KNOB("ET_GATHER_W", 4);
-            const int64_t pw = w * (64 / LPR) * uo;
-            const int64_t g1 = (batch + pw - 1) / pw * n;
-            if (g1 > 0x7fffffffll) return fail(ET_ERR_ARG, "grid too large");
-#define ET_G1(UU, WW)                                                                            \
-    if (uo == UU && w == WW) {                                                                   \
-        if (ntl)                                                                                 \
-            hipLaunchKernelGGL((k_gather_one<RB, NT, true, UU, WW>), dim3((unsigned)g1),        \
-                               dim3(64 * WW), 0, s, pack, n, batch,                              \
-                               reinterpret_cast<char*>(dst), ld_dst * es, es);                   \
-        else                                                                                     \
-            hipLaunchKernelGGL((k_gather_one<RB, NT, false, UU, WW>), dim3((unsigned)g1),       \
-                               dim3(64 * WW), 0, s, pack, n, batch,                              \
-                               reinterpret_cast<char*>(dst), ld_dst * es, es);                   \
-        ET_LAUNCH_CHECK("k_gather_one");                                                         \
-        return ET_OK;                                                                            \
-    }
-            ET_G1(4, 4) ET_G1(16, 4) ET_G1(32, 4) ET_G1(6, 4) ET_G1(12, 4)
-            ET_G1(8, 2) ET_G1(8, 8) ET_G1(8, 1) ET_G1(16, 2) ET_G1(4, 8)
-#undef ET_G1
-        }
-#endif
-        if (one) {  // the default: one round of 8 rows per lane group, 4 waves per workgroup
-            constexpr int kU = 8, kW = 4;
-            const int64_t pw = kW * (64 / LPR) * kU;
-            const int64_t g1 = (batch + pw - 1) / pw * n;
-            if (g1 <= 0) return ET_OK;
-            if (g1 > 0x7fffffffll) return fail(ET_ERR_ARG, "grid too large");
-            if (ntl)
-                hipLaunchKernelGGL((k_gather_one<RB, NT, true, kU, kW>), dim3((unsigned)g1),
-                                   dim3(64 * kW), 0, s, pack, n, batch,
-                                   reinterpret_cast<char*>(dst), ld_dst * es, es);
-            else
-                hipLaunchKernelGGL((k_gather_one<RB, NT, false, kU, kW>), dim3((unsigned)g1),
-                                   dim3(64 * kW), 0, s, pack, n, batch,
-                                   reinterpret_cast<char*>(dst), ld_dst * es, es);
-            ET_LAUNCH_CHECK("k_gather_one");
-            return ET_OK;
-        }
+        // one round of 8 rows per lane group, 4 waves per workgroup
+        constexpr int kU = 8, kW = 4;
+        const int64_t pw = kW * (64 / LPR) * kU;
+        const int64_t g1 = (batch + pw - 1) / pw * n;
+        if (g1 <= 0) return ET_OK;
+        if (g1 > 0x7fffffffll) return fail(ET_ERR_ARG, "grid too large");
+        if (ntl)
+            hipLaunchKernelGGL((k_gather_one<RB, NT, true, kU, kW>), dim3((unsigned)g1),
+                               dim3(64 * kW), 0, s, pack, n, batch, reinterpret_cast<char*>(dst),
+                               ld_dst * es, es);
+        else
+            hipLaunchKernelGGL((k_gather_one<RB, NT, false, kU, kW>), dim3((unsigned)g1),
+                               dim3(64 * kW), 0, s, pack, n, batch, reinterpret_cast<char*>(dst),
+                               ld_dst * es, es);
+        ET_LAUNCH_CHECK("k_gather_one");
+        return ET_OK;
     }
     const int rounds = rounds_for(batch, per_round, n);
     const int64_t nchunks = (batch + per_round * rounds - 1) / (per_round * rounds);
@@ -1668,8 +1174,8 @@ int launch_pooled_masked(const LookupPack& pack, int n, int D, int64_t batch, vo
 #define ET_MK(C)                                                                              \
     case C:                                                                                   \
         if constexpr (C / (16 / (int)sizeof(T)) >= 1)                                         \
-            return launch_pooled_vec_u<T, A, C, VecGeom<T, C>::U, NT, false, true>(           \
-                pack, n, batch, dst, ld_dst, s);                                              \
+            return launch_pooled_vec<T, A, C, NT, false, true>(pack, n, batch, dst, ld_dst,   \
+                                                               s);                            \
         break;
     switch (masked_capacity(D)) {
         ET_MK(16)

@@ -1,5 +1,5 @@
-"""The vector-index gather (k_gather_one, et_lookup.hip; round 5's pipelined k_gather_pipe
-before it): one round of 8 rows per lane group, each row stored as it arrives.  Bit copies of
+"""The vector-index gather (k_gather_one, et_lookup.hip; round 5's pipelined two-round kernel
+before it, since removed): one round of 8 rows per lane group, each row stored as it arrives.  Bit copies of
 the oracle's gather (src/lookup.jl:51-87) at every row size the kernel takes (128 .. 1024
 bytes), batches that end inside a workgroup and a row group, a strided destination, several
 tables in one launch and out-of-range indices (zero rows, counted)."""

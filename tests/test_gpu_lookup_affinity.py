@@ -5,8 +5,8 @@ and a CACHE class (tables an XCD's L2 holds); a workgroup claims from the class 
 falls back through the other heads (csrc/et_lookup.hip).  Which workgroup sums which bags must
 never change a result, so every case is compared bit for bit with oracle.maplookup_prealloc —
 no tolerance.  Everything goes through et_maplookup_prealloc_q on a caller-owned queue block,
-whose 128 bytes must read back zero after every launch (the reset covers both heads of every
-XCD and the resident counters).
+whose 128 bytes must read back zero after every launch (the reset covers the whole block: both
+heads of every XCD, the done counter and the padding).
 
 With 512-byte rows "fabric" is more than 8,192 rows and "cache" at most 8,192.  The small
 batches leave most XCD queues empty, so every fallback step of the claim order is taken; the odd
@@ -48,7 +48,8 @@ def _block_is_zero(q):
 
 
 class Launch:
-    """One et_maplookup_prealloc_q call over device tables `tabs` and host indices `hidx`."""
+    """One et_maplookup_prealloc_q call over device tables `tabs` and host indices `hidx`
+    (et_maplookup_prealloc when called without a queue block)."""
 
     def __init__(self, tabs, hidx):
         self.tabs = tabs
@@ -67,9 +68,13 @@ class Launch:
 
     def __call__(self, q, dst=None):
         dst = self.new_dst() if dst is None else dst
-        _lib.check(_lib.load().et_maplookup_prealloc_q(
-            self.code, ctypes.addressof(self.descs), self.n, self.B, dst.data_ptr(),
-            self.D * self.n, 0, q.data_ptr(), _lib.stream_handle()))
+        args = (self.code, ctypes.addressof(self.descs), self.n, self.B, dst.data_ptr(),
+                self.D * self.n, 0)
+        if q is None:
+            _lib.check(_lib.load().et_maplookup_prealloc(*args, _lib.stream_handle()))
+        else:
+            _lib.check(_lib.load().et_maplookup_prealloc_q(*args, q.data_ptr(),
+                                                           _lib.stream_handle()))
         return dst
 
 
@@ -159,10 +164,37 @@ def test_two_streams_two_blocks(oracle, mixed):
     (np.float64, 64, MIXED_ROWS),
     # 256-byte rows (k_pooled_vec_queued<SG = false>): the fabric class starts above 16,384 rows
     (np.float32, 64, [16400, 40000, 18000, 4099, 300, 50, 7, 1]),
-], ids=["f16x256", "f64x64", "f32x64"])
+    (np.float16, 128, [16400, 40000, 18000, 4099, 300, 50, 7, 1]),
+], ids=["f16x256", "f64x64", "f32x64", "f16x128"])
 def test_other_element_paths(oracle, dtype, D, rows):
     hs, tabs = _tables(rows, D, dtype, 79)
     _check(oracle, hs, tabs, _indices(rows, 257, 13, 80))
+
+
+ROWS_256B = [(np.float32, 64), (np.float16, 128)]  # 256-byte rows: always the per-lane loop
+
+
+@pytest.mark.parametrize("dtype,D", ROWS_256B, ids=["f32x64", "f16x128"])
+def test_256_byte_rows_static_stripes(oracle, dtype, D):
+    """No queue block: k_pooled_vec_striped<SG = false>.  One table above 4 MiB (16,384 rows)."""
+    rows = [16400, 300, 7]
+    hs, tabs = _tables(rows, D, dtype, 82)
+    hidx = _indices(rows, 65, 5, 83)
+    et.check_errors()
+    got = Launch(tabs, hidx)(None)
+    assert et.check_errors() == 0
+    assert _same(got, oracle.maplookup_prealloc(hs, hidx))
+
+
+@pytest.mark.parametrize("dtype,D", ROWS_256B, ids=["f32x64", "f16x128"])
+def test_256_byte_rows_single_table(oracle, dtype, D):
+    """One table: the linear k_pooled_vec<SG = false>."""
+    hs, tabs = _tables([300], D, dtype, 84)
+    hidx = _indices([300], 9, 3, 85)
+    et.check_errors()
+    got = Launch(tabs, hidx)(None)
+    assert et.check_errors() == 0
+    assert _same(got, oracle.pooled_sum(hs[0], hidx[0]))
 
 
 def test_out_of_range_indices(oracle, mixed):

@@ -79,5 +79,11 @@ def test_wrong_result_knob_and_dead_walks_are_gone():
                  "fed_gather_asm", "k_sgd_chains_fed", "hf_pair",
                  # the losing variants of the update pipeline (DESIGN.md keeps their numbers)
                  "k_sgd_chains_w", "ET_EH_WIDE", "ET_WORK_STREAM", "ET_PLAN_SIDE", "ET_SGD_OCC5",
-                 "ET_SGD_SINGLES", "ET_SIDE_HIGH", "kWork"):
+                 "ET_SGD_SINGLES", "ET_SIDE_HIGH", "kWork",
+                 # the losing variants of the lookup unit (DESIGN.md keeps their numbers)
+                 "ET_SG256", "SgVec", "sg_bpl", "u32x2", "ET_HEAD_NOADD", "ET_NTIDX", "ET_FSPLIT",
+                 "run_bags_slice", "ET_CACHE_CAP", "ET_QORDER", "k_pooled_vec_striped_w8", "ET_W8",
+                 "launch_pooled_vec_u", "rows_in_flight", "k_gather_s512", "ET_GATHER_S",
+                 "k_gather_pipe", "ET_GATHER_PIPE", "ET_G1", "ET_GATHER_ONE", "ET_GATHER_W",
+                 '"ET_U"', "ET_BCAST_READLANE_MAX_GPW"):
         assert gone not in src, gone

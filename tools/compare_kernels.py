@@ -1,9 +1,13 @@
 #!/usr/bin/env python3
 """Are the gfx950 kernels of two builds of the library the same code?
 
-usage: python tools/compare_kernels.py OLD.so NEW.so [REMOVED_SUBSTRING ...]
+usage: python tools/compare_kernels.py [--rename REGEX REPL]... OLD.so NEW.so [REMOVED_SUBSTRING ...]
 (run by path, from any directory; REMOVED_SUBSTRING matches mangled names, so give the length
 prefix too: 12k_sgd_chunksI is k_sgd_chunks<...> and not k_sgd_chunks5 or k_sgd_chunks_generic)
+
+--rename pairs a kernel whose template parameters changed with its new name: re.sub(REGEX, REPL)
+is applied to every mangled name of OLD before anything is compared, so a renamed kernel is
+compared exactly like an unrenamed one.  Two OLD kernels may not end up with one name.
 
 For a change that must not touch device code (a refactor of the host side, a removal of
 dead variants): the kernel symbols of NEW must be those of OLD minus the ones containing a
@@ -38,23 +42,35 @@ def normalise(text: str) -> list:
     return out
 
 
-def load(lib: str):
-    meta = {k["name"]: tuple(k.get(m) for m in META) for k in com.kernels(lib)}
-    dis = com.disassembly(lib)
-    return meta, {n: normalise(dis.get(n, "")) for n in meta}
+def load(lib: str, renames=()):
+    def name(n):
+        for pat, repl in renames:
+            n = re.sub(pat, repl, n)
+        return n
+
+    meta, dis = {}, com.disassembly(lib)
+    for k in com.kernels(lib):
+        if name(k["name"]) in meta:
+            sys.exit(f"--rename gives two kernels one name: {name(k['name'])}")
+        meta[name(k["name"])] = tuple(k.get(m) for m in META)
+    return meta, {name(n): normalise(t) for n, t in dis.items() if name(n) in meta}
 
 
 def main() -> int:
-    old_meta, old_dis = load(sys.argv[1])
-    new_meta, new_dis = load(sys.argv[2])
-    removed = sys.argv[3:]
+    argv, renames = sys.argv[1:], []
+    while argv and argv[0] == "--rename":
+        renames.append((argv[1], argv[2]))
+        argv = argv[3:]
+    old_meta, old_dis = load(argv[0], renames)
+    new_meta, new_dis = load(argv[1])
+    removed = argv[2:]
     gone = set(old_meta) - set(new_meta)
     bad = [f"added: {n}" for n in sorted(set(new_meta) - set(old_meta))]
     bad += [f"missing: {n}" for n in sorted(gone) if not any(r in n for r in removed)]
     for n in sorted(set(old_meta) & set(new_meta)):
         if old_meta[n] != new_meta[n]:
             bad.append(f"metadata {dict(zip(META, old_meta[n]))} -> {new_meta[n]}: {n}")
-        if old_dis[n] != new_dis[n] or not new_dis[n]:
+        if old_dis.get(n) != new_dis.get(n) or not new_dis.get(n):
             bad.append(f"disassembly: {n}")
     per = collections.Counter(r for n in gone for r in removed if r in n)
     print(f"kernels: {len(old_meta)} -> {len(new_meta)}; removed {len(gone)} {dict(per)}; "

@@ -1,7 +1,6 @@
 #!/bin/bash
 # The EXPERIMENT build of the library: -DET_EXPERIMENTS compiles the tuning knobs' environment
-# reads back in (ET_KNOB, csrc/et_common.h), the non-default kernel variants (the ET_W8 /
-# ET_U lookup kernels, the queue orders) and the chain-item timeline
+# reads back in (ET_KNOB, csrc/et_common.h) and the chain-item timeline
 # (et_debug_chain_timeline).  Output: tools/exp/libembtab_hip_exp.so, loaded with
 #   ET_LIBRARY=tools/exp/libembtab_hip_exp.so ET_<KNOB>=<value> python ...
 # The package's own library (embtab/libembtab_hip.so) never reads the environment.

@@ -89,7 +89,7 @@ def cu_affinity(s, e, c, xcc, hw, home, fab_share):
 
 def main():
     # ET_TL_LIBRARY: another profiling build (tools/wg_timeline.sh TL_NAME=..., e.g. with the
-    # experiment knobs: ET_AFFINITY, ET_FAB_SHARE, ET_CACHE_CAP are then read by the library)
+    # experiment knobs: ET_AFFINITY, ET_FAB_SHARE are then read by the library)
     os.environ["ET_LIBRARY"] = os.environ.get("ET_TL_LIBRARY") or os.path.join(
         REPO, "tools", "tl", "libembtab_hip.so")
     os.environ["ET_TOOLS_EXPERIMENT"] = "1"
