@@ -15,7 +15,7 @@ from .ragged import RaggedIndices
 from .lookup import (AbstractExecutionStrategy, DefaultStrategy, NoTangent,
                      PreallocationPlan, PreallocationStrategy, SimpleParallelStrategy, colwrap, destination, lookup,
                      lookup_, maplookup, maplookup_)
-from .update import (AbstractIndexer, DenseIndexer, Descent, Indexer, IndexerView, PhasedUpdate,
+from .update import (AbstractIndexer, AdaGrad, DenseIndexer, Descent, Indexer, IndexerView, PhasedUpdate,
                      SparseEmbeddingUpdate, SparseIndexer, ensemble_update, gettranslations,
                      index_, optimise_update_, rrule, uncompress, update_)
 
@@ -30,5 +30,5 @@ __all__ = [
     "rrule", "Descent", "AbstractIndexer", "Indexer", "SparseIndexer", "DenseIndexer",
     "IndexerView", "index_", "gettranslations", "update_", "optimise_update_",
     "ensemble_update", "PhasedUpdate", "EmbtabError", "check_errors",
-    "RaggedIndices",
+    "RaggedIndices", "AdaGrad",
 ]

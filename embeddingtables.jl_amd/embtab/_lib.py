@@ -31,6 +31,7 @@ ET_FLAG_SGD_F64_ALPHA = 16
 ET_FLAG_SGD_INDEX_ONLY = 32
 ET_FLAG_SGD_APPLY_ONLY = 64
 ET_FLAG_SGD_HOT_PASS = 128
+ET_FLAG_ADAGRAD_ROWWISE = 512
 ET_MAX_TABLES_PER_LAUNCH = 32
 ET_SGD_CHUNK = 256  # include/embtab.h: occurrences per chunk of the non-exact SGD
 ET_ABI_VERSION = 9
@@ -68,6 +69,8 @@ EXPORTS = (
     "et_ragged_bag_ids",
     "et_ragged_sgd_workspace_size",
     "et_ragged_sgd",
+    "et_adagrad_workspace_size",
+    "et_sparse_adagrad",
     "et_concat_slabs",
     "et_split_slabs",
     "et_push_cols",
@@ -177,6 +180,28 @@ class RaggedUpdateDesc(ctypes.Structure):
     ]
 
 
+class AdaGradDesc(ctypes.Structure):
+    """et_adagrad_desc (include/embtab.h)."""
+
+    _fields_ = [
+        ("table", ctypes.c_void_p),
+        ("ld_table", ctypes.c_int64),
+        ("nrows", ctypes.c_int64),
+        ("dim", ctypes.c_int32),
+        ("pool", ctypes.c_int32),
+        ("delta", ctypes.c_void_p),
+        ("ld_delta", ctypes.c_int64),
+        ("idx", ctypes.c_void_p),
+        ("ld_idx", ctypes.c_int64),
+        ("batch", ctypes.c_int64),
+        ("cols_per_page", ctypes.c_int64),
+        ("colptr", ctypes.c_void_p),
+        ("nnz", ctypes.c_int64),
+        ("state", ctypes.c_void_p),
+        ("ld_state", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -219,6 +244,8 @@ def load() -> ctypes.CDLL:
         "et_ragged_bag_ids": ([vp, i64, i64, vp, vp], c_int),
         "et_ragged_sgd_workspace_size": ([vp, i32, vp], c_int),
         "et_ragged_sgd": ([c_int, vp, i32, dbl, u32, vp, i64, vp], c_int),
+        "et_adagrad_workspace_size": ([vp, i32, vp], c_int),
+        "et_sparse_adagrad": ([c_int, vp, i32, dbl, dbl, u32, vp, i64, vp], c_int),
         "et_concat_slabs": ([c_int, vp, i32, i64, i64, vp, vp, vp, i64, vp], c_int),
         "et_split_slabs": ([c_int, vp, i64, i64, i32, vp, vp, vp, i64, vp], c_int),
         "et_push_cols": ([c_int, vp, i64, i64, i64, i64, vp, i32, vp], c_int),

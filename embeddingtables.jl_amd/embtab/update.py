@@ -15,6 +15,7 @@ from __future__ import annotations
 import collections
 import ctypes
 import threading
+import weakref
 
 import torch
 
@@ -120,6 +121,59 @@ class Descent:
 
     def __repr__(self):
         return f"Descent({self.eta})"
+
+
+class AdaGrad:
+    """Sparse AdaGrad (et_sparse_adagrad, include/embtab.h states the arithmetic): per
+    updated column ``s' = s + g*g``, ``w' = w - eta*g / (sqrt(s') + eps)`` element-wise (Flux's
+    ``ADAGrad``), or with ``rowwise=True`` one accumulator per column, ``s' = s + mean(g*g)``.
+    Beyond the reference (its only optimiser is Descent): parity with Flux is unpinned.
+
+    The state lives in this object, one tensor per table object: ``state(table)`` is
+    ``(R, D)``, or ``(R,)`` row-wise, Float32 (Float64 for Float64 tables), filled with
+    ``initial_accumulator_value`` on first use and always one contiguous allocation whatever
+    the table's storage.  It is allocated outside the C call, as ``device_table()`` is: call
+    ``opt.state(A)`` (or run one eager step) before capturing ``update_`` into a HIP graph.
+    ``set_state(table, tensor)`` installs a caller-owned tensor instead (a row block of a
+    wider one is fine: unit feature stride, any row stride >= D)."""
+
+    def __init__(self, eta: float = 0.1, eps: float = 1e-8, rowwise: bool = False,
+                 initial_accumulator_value: float = 0.0):
+        self.eta = float(eta)
+        self.eps = float(eps)
+        self.rowwise = bool(rowwise)
+        self.initial_accumulator_value = float(initial_accumulator_value)
+        self._state = weakref.WeakKeyDictionary()
+
+    def __repr__(self):
+        return f"AdaGrad({self.eta}, {self.eps}{', rowwise' if self.rowwise else ''})"
+
+    @staticmethod
+    def _state_dtype(table):
+        return torch.float64 if table.dtype == torch.float64 else torch.float32
+
+    def _shape(self, table):
+        D, R = table.size()
+        return (R,) if self.rowwise else (R, D)
+
+    def state(self, table: AbstractEmbeddingTable) -> torch.Tensor:
+        s = self._state.get(table)
+        if s is None:
+            s = torch.full(self._shape(table), self.initial_accumulator_value,
+                           dtype=self._state_dtype(table), device=table.device)
+            self._state[table] = s
+        return s
+
+    def set_state(self, table: AbstractEmbeddingTable, s: torch.Tensor) -> torch.Tensor:
+        if tuple(s.shape) != self._shape(table) or s.dtype != self._state_dtype(table):
+            raise ArgumentError(f"state of shape {tuple(s.shape)} / {s.dtype}, expected "
+                                f"{self._shape(table)} / {self._state_dtype(table)}")
+        if s.device != table.device:
+            raise ArgumentError("state and table live on different devices")
+        if s.numel() > 0 and s.stride(-1) != 1:
+            raise ArgumentError("state features must be contiguous")
+        self._state[table] = s
+        return s
 
 
 # --- workspaces ------------------------------------------------------------------------------
@@ -455,7 +509,29 @@ def update_(*args, nontemporal: bool | None = None, exact: bool | None = None,
     et_ragged_sgd: always the exact serial sum whatever ``exact`` says (a hot column is one
     serial chain on one wave), no hot pass.  In a multi-table call the ragged tables are
     updated in one call per (path, eltype) group ahead of the others, which take the usual
-    path; a ``telemetry_cb`` runs after the ragged tables' update is enqueued."""
+    path; a ``telemetry_cb`` runs after the ragged tables' update is enqueued.
+
+    * ``update_(opt::AdaGrad, table, grad)`` and ``update_(opt::AdaGrad, tables, grads)`` —
+      sparse AdaGrad (et_sparse_adagrad), fixed-pool and ragged gradients in the same call,
+      one call per element type and at most ET_MAX_TABLES_PER_LAUNCH tables.  ``nontemporal``
+      is its only keyword: ``exact``, ``hot_pass``, ``f16_fp32_acc``, ``indexer`` /
+      ``indexers`` and ``telemetry_cb`` belong to the SGD and raise ``ArgumentError``."""
+    if args and isinstance(args[0], AdaGrad):
+        refused = {"exact": exact is not None, "f16_fp32_acc": bool(f16_fp32_acc),
+                   "hot_pass": bool(hot_pass), "indexer / indexers (positional)": len(args) > 3}
+        refused.update({k: True for k in kw})
+        for name, given in refused.items():
+            if given:
+                raise ArgumentError(f"update_ with AdaGrad takes no `{name}`: nontemporal is "
+                                    "its only keyword")
+        if len(args) < 3:
+            raise ArgumentError("update_(opt, table, grad) or update_(opt, tables, grads)")
+        nt = True if nontemporal is None else bool(nontemporal)
+        if isinstance(args[1], AbstractEmbeddingTable):
+            _update_adagrad(args[0], [args[1]], [args[2]], nt)
+        else:
+            _update_adagrad(args[0], list(args[1]), list(args[2]), nt)
+        return None
     if exact is None:
         exact = EXACT_DEFAULT
     if args and isinstance(args[0], Descent):
@@ -621,6 +697,53 @@ def _update_multi(opt: Descent, tables, grads, nontemporal: bool, exact: bool | 
                                        ws.numel(), stream))
 
 
+def _adagrad_desc(opt: AdaGrad, table, grad: SparseEmbeddingUpdate) -> _lib.AdaGradDesc:
+    S = opt.state(table)
+    ld_state = 1 if opt.rowwise else (int(S.stride(0)) if S.shape[0] > 1 else int(S.shape[1]))
+    if isinstance(grad.indices, RaggedIndices):
+        r = _ragged_update_desc(table, grad)
+        return _lib.AdaGradDesc(r.table, r.ld_table, r.nrows, r.dim, 1, r.delta, r.ld_delta,
+                                r.idx, 1, r.batch, r.cols_per_page, r.colptr, r.nnz,
+                                S.data_ptr(), ld_state)
+    u = _update_desc(table, grad)
+    return _lib.AdaGradDesc(u.table, u.ld_table, u.nrows, u.dim, u.pool, u.delta, u.ld_delta,
+                            u.idx, u.ld_idx, u.batch, u.cols_per_page, None, 0, S.data_ptr(),
+                            ld_state)
+
+
+def _update_adagrad(opt: AdaGrad, tables, grads, nontemporal: bool):
+    """One et_sparse_adagrad call per element type and at most ET_MAX_TABLES_PER_LAUNCH
+    tables; fixed-pool and ragged gradients stay in the same call, empty ones are skipped."""
+    if len(tables) != len(grads):
+        raise ArgumentError("tables and grads differ in length")
+    groups: dict = {}
+    for A, g in zip(tables, grads):
+        I = g.indices
+        if isinstance(I, RaggedIndices):
+            if I.nnz == 0 or I.batch == 0:
+                continue
+        elif I.numel() == 0:
+            continue
+        groups.setdefault(A.dtype, []).append(_adagrad_desc(opt, A, g))
+    flags = (_lib.ET_FLAG_NONTEMPORAL if nontemporal else 0) | (
+        _lib.ET_FLAG_ADAGRAD_ROWWISE if opt.rowwise else 0)
+    L = _lib.load()
+    ncall = 0
+    for dtype, descs in groups.items():
+        for c in range(0, len(descs), _lib.ET_MAX_TABLES_PER_LAUNCH):
+            part = descs[c:c + _lib.ET_MAX_TABLES_PER_LAUNCH]
+            arr = (_lib.AdaGradDesc * len(part))(*part)
+            nb = ctypes.c_int64(0)
+            _lib.check(L.et_adagrad_workspace_size(ctypes.addressof(arr), len(part),
+                                                   ctypes.byref(nb)))
+            dev = tables[0].device
+            ws = _workspace(nb.value, dev, f"adagrad{ncall}")
+            _lib.check(L.et_sparse_adagrad(_lib.TORCH_TO_ET[dtype], ctypes.addressof(arr),
+                                           len(part), opt.eta, opt.eps, flags, ws.data_ptr(),
+                                           ws.numel(), _lib.stream_handle(dev)))
+            ncall += 1
+
+
 def _update_from_indexer(table, grad: SparseEmbeddingUpdate, indexer: AbstractIndexer,
                          alpha: float, nontemporal: bool, f16_fp32_acc: bool = False):
     base = indexer.I if isinstance(indexer, IndexerView) else indexer
@@ -710,6 +833,8 @@ class PhasedUpdate:
     def update_(self, opt: Descent, stream=None):
         """Phase 2 on ``stream`` (default: the current stream), ordered after the last
         ``index_``.  May be repeated (same indices, new gradient values)."""
+        if isinstance(opt, AdaGrad):
+            raise ArgumentError("PhasedUpdate is SGD-only: AdaGrad has no phased form")
         if self.device is None:
             return None
         if self._indexed is None:

@@ -697,6 +697,114 @@ function update!(opt::Flux.Descent, table::HipTable{S,T}, grad::RaggedEmbeddingU
 end
 
 #####
+##### Sparse AdaGrad (no counterpart in the reference, whose only optimiser is Descent;
+##### include/embtab.h states the arithmetic, parity with Flux.ADAGrad is unpinned).  The
+##### state lives in the optimiser, one device array per table object: dim x nrows
+##### element-wise, nrows entries row-wise, Float32 (Float64 for Float64 tables).
+#####
+
+const ET_FLAG_ADAGRAD_ROWWISE = UInt32(512)
+
+struct AdaGradDesc
+    table::Ptr{Cvoid}
+    ld_table::Int64
+    nrows::Int64
+    dim::Int32
+    pool::Int32
+    delta::Ptr{Cvoid}
+    ld_delta::Int64
+    idx::Ptr{Int64}
+    ld_idx::Int64
+    batch::Int64
+    cols_per_page::Int64
+    colptr::Ptr{Int64}
+    nnz::Int64
+    state::Ptr{Cvoid}
+    ld_state::Int64
+end
+
+mutable struct SparseAdaGrad
+    eta::Float64
+    eps::Float64
+    rowwise::Bool
+    initial_accumulator_value::Float64
+    states::IdDict{Any,Any}
+end
+SparseAdaGrad(eta = 0.1; eps = 1e-8, rowwise = false, initial_accumulator_value = 0.0) =
+    SparseAdaGrad(eta, eps, rowwise, initial_accumulator_value, IdDict{Any,Any}())
+
+_state_eltype(::Type{Float64}) = Float64
+_state_eltype(::Type) = Float32
+
+# The state of `table`, created on first use (call it before capturing a HIP graph).
+function state(opt::SparseAdaGrad, table::HipTable{S,T}) where {S,T}
+    get!(opt.states, table) do
+        C = _state_eltype(T)
+        dims = opt.rowwise ? (size(table, 2),) : size(table)
+        upload(fill(C(opt.initial_accumulator_value), dims))
+    end
+end
+
+function _adagrad_desc(opt::SparseAdaGrad, A::HipTable, g::SparseEmbeddingUpdate)
+    u = _update_desc(A, g)
+    s = state(opt, A)
+    return AdaGradDesc(u.table, u.ld_table, u.nrows, u.dim, u.pool, u.delta, u.ld_delta, u.idx,
+                       u.ld_idx, u.batch, u.cols_per_page, Ptr{Int64}(C_NULL), 0,
+                       Ptr{Cvoid}(s.ptr), size(A, 1))
+end
+
+function _adagrad_desc(opt::SparseAdaGrad, A::HipTable, g::RaggedEmbeddingUpdate)
+    dp, dld = _ptr_ld(g.delta)
+    tp, ldt, cpp = _device_table(A)
+    R = g.indices
+    s = state(opt, A)
+    return AdaGradDesc(tp, ldt, size(A, 2), size(A, 1), 1, dp, dld, R.values.ptr, 1,
+                       batchsize(R), cpp, R.colptr.ptr, length(R.values), Ptr{Cvoid}(s.ptr),
+                       size(A, 1))
+end
+
+function _sparse_adagrad(::Type{T}, opt::SparseAdaGrad, descs::Vector{AdaGradDesc},
+                         nontemporal::Bool) where {T}
+    isempty(descs) && return nothing
+    flags = (nontemporal ? ET_FLAG_NONTEMPORAL : UInt32(0)) |
+            (opt.rowwise ? ET_FLAG_ADAGRAD_ROWWISE : UInt32(0))
+    nb = Ref{Int64}(0)
+    check(ccall((:et_adagrad_workspace_size, libembtab), Cint,
+                (Ptr{AdaGradDesc}, Int32, Ref{Int64}), descs, length(descs), nb))
+    ws = _workspace(nb[], -3)
+    check(ccall((:et_sparse_adagrad, libembtab), Cint,
+                (Cint, Ptr{AdaGradDesc}, Int32, Float64, Float64, UInt32, Ptr{Cvoid}, Int64,
+                 Ptr{Cvoid}),
+                et_dtype(T), descs, length(descs), opt.eta, opt.eps, flags, ws.ptr, length(ws),
+                stream()))
+    return nothing
+end
+
+const AdaGradUpdate = Union{SparseEmbeddingUpdate,RaggedEmbeddingUpdate}
+
+function update!(opt::SparseAdaGrad, table::HipTable{S,T}, grad::AdaGradUpdate,
+                 ::Val{Nontemporal} = Val(true)) where {S,T<:UpdateEltype,Nontemporal}
+    isempty(grad.indices) && return nothing
+    return _sparse_adagrad(T, opt, [_adagrad_desc(opt, table, grad)], Nontemporal)
+end
+
+# Fixed-pool and ragged gradients stay in one call: one call per element type and at most 32
+# tables (ET_MAX_TABLES_PER_LAUNCH); empty gradients are skipped.
+function update!(opt::SparseAdaGrad, tables::AbstractVector{<:HipTable}, grads::AbstractVector,
+                 ::Val{Nontemporal} = Val(true)) where {Nontemporal}
+    length(tables) == length(grads) || throw(ArgumentError("tables and grads differ in length"))
+    groups = Dict{DataType,Vector{AdaGradDesc}}()
+    for (A, g) in zip(tables, grads)
+        isempty(g.indices) && continue
+        push!(get!(groups, eltype(A), AdaGradDesc[]), _adagrad_desc(opt, A, g))
+    end
+    for (T, descs) in groups, c in 1:32:length(descs)
+        _sparse_adagrad(T, opt, descs[c:min(c + 31, length(descs))], Nontemporal)
+    end
+    return nothing
+end
+
+#####
 ##### Sharded Preallocation maplookup over the GPUs of a node (BASELINE config 5):
 ##### one Julia process per GPU, RCCL over xGMI (include/embtab.h, csrc/et_shard.cpp)
 #####

@@ -366,6 +366,79 @@ int et_ragged_sgd_workspace_size(const et_ragged_update_desc* descs, int32_t nta
 int et_ragged_sgd(int dtype, const et_ragged_update_desc* descs, int32_t ntables, double eta,
                   uint32_t flags, void* workspace, int64_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Sparse AdaGrad, element-wise (Flux's ADAGrad) and row-wise, over fixed-pool and ragged
+ * gradients.  The reference has no optimiser but Descent: this arithmetic is defined here,
+ * and its parity with Flux is unpinned (as Float16 parity is).
+ *
+ * For every table t and every distinct column r with at least one participating
+ * occurrence, in the accumulator type C (Float32 for F32 / F16 / BF16 tables, Float64 for
+ * F64), eta_c and eps_c being eta and eps rounded to C:
+ *
+ *   gradient sum g.  The column's occurrence list is in occurrence order for a fixed-pool
+ *   index (as et_sparse_sgd sees it) and in increasing entry k for a ragged one.  It is cut
+ *   into consecutive chunks of ET_SGD_CHUNK list positions; p_c = +0, then
+ *   p_c += delta[:, bag] for the chunk's occurrences in order; g = p_0 for one chunk,
+ *   g = ((p_0 + p_1) + p_2) + ... in chunk order otherwise.  A column of at most ET_SGD_CHUNK
+ *   occurrences is therefore the reference's serial sum (src/sparseupdate.jl:97-129); a hot
+ *   column is ordered partial sums, never one serial chain.  A ragged entry with no bag (the
+ *   capacity tail) adds nothing BUT KEEPS ITS LIST POSITION: the rounding of a column with
+ *   more than ET_SGD_CHUNK entries depends on what sits in the tail.
+ *
+ *   element-wise:  s' = s + g*g ;  d = sqrt(s') + eps_c ;  w' = T(C(w) - (eta_c*g)/d)
+ *   row-wise (ET_FLAG_ADAGRAD_ROWWISE): one state per column, m = (sum_f g_f^2) / dim
+ *   evaluated in C (the order of that sum is the kernel's choice), s' = s + m, then d and
+ *   w' as above with the scalar s'.
+ *
+ * Every operation is rounded once in C, nothing is contracted, sqrt and / are correctly
+ * rounded, subnormals are kept; F16 / BF16 results are rounded to T once (RNE).  A column
+ * with no participating occurrence is not written, and neither is its state.
+ * ------------------------------------------------------------------------------- */
+#define ET_FLAG_ADAGRAD_ROWWISE 512u /* et_sparse_adagrad: one accumulator per column */
+
+/* One table of a sparse AdaGrad update: the fields of et_update_desc, the ragged form's
+ * colptr / nnz, and the optimiser state. */
+typedef struct et_adagrad_desc {
+    void* table;           /* device pointer, updated in place */
+    int64_t ld_table;
+    int64_t nrows;
+    int32_t dim;
+    int32_t pool;          /* indices per bag of a fixed-pool index; ignored when ragged */
+    const void* delta;     /* dim x batch gradient, column j at delta + j*ld_delta */
+    int64_t ld_delta;
+    const int64_t* idx;    /* fixed pool: the P x B indices; ragged: the values */
+    int64_t ld_idx;        /* fixed pool only */
+    int64_t batch;         /* bags (gradient columns) */
+    int64_t cols_per_page; /* as in et_lookup_desc */
+    const int64_t* colptr; /* NULL: a fixed pool.  Else batch + 1 entries, as et_ragged_desc */
+    int64_t nnz;           /* ragged: capacity of idx */
+    void* state;           /* device, type C, updated in place: dim x nrows with leading
+                              dimension ld_state (element-wise) or nrows entries (row-wise).
+                              Always ONE contiguous allocation, whatever the table's storage;
+                              must not overlap the table */
+    int64_t ld_state;      /* elements between the states of consecutive columns (>= dim);
+                              ignored by the row-wise form */
+} et_adagrad_desc;
+
+/* Bytes of device workspace et_sparse_adagrad needs for these descriptors (grows with the
+ * occurrences: pool * batch, or nnz for a ragged table; any alignment, as
+ * et_sgd_workspace_size; the same for both forms and every element type). */
+int et_adagrad_workspace_size(const et_adagrad_desc* descs, int32_t ntables, int64_t* bytes);
+
+/* Sparse AdaGrad over one or many tables, fixed-pool and ragged ones in one call (semantics
+ * above).  ET_F32 / ET_F64 / ET_F16 / ET_BF16 (anything else: ET_ERR_UNSUPPORTED); the table
+ * and delta share the element type.  Flags: ET_FLAG_NONTEMPORAL (stores of the updated rows
+ * and states) and ET_FLAG_ADAGRAD_ROWWISE; the SGD's flags (ET_FLAG_EXACT_UPDATE,
+ * ET_FLAG_EXACT_IF_FAST, ET_FLAG_F16_FP32_ACC, ET_FLAG_SGD_*) return ET_ERR_UNSUPPORTED.
+ * ET_ERR_ARG before any device work: a NULL state, ld_state < dim (element-wise), a state
+ * that overlaps its table, negative sizes, more than ET_MAX_TABLES_PER_LAUNCH tables.
+ * An index outside 1..nrows is counted (et_check_errors) and writes nothing.  Stream-ordered
+ * on the caller's stream only (no side streams, no host synchronisation): capturable.
+ * The occurrences of all tables together must stay below 2^31 - 1. */
+int et_sparse_adagrad(int dtype, const et_adagrad_desc* descs, int32_t ntables, double eta,
+                      double eps, uint32_t flags, void* workspace, int64_t ws_bytes,
+                      void* stream);
+
 /* Assemble the Preallocation concat from per-rank slabs after an all-gather
  * (table-wise sharding across GPUs, no counterpart in the single-process
  * reference): slab r is a (slab_ld x batch) column-major block at
