@@ -21,6 +21,7 @@
 //     allocation, hipGraph-capturable).
 #include <type_traits>
 #include "et_common.h"
+#include "et_lookup_order.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -510,10 +511,12 @@ __global__ __launch_bounds__(256) void k_pooled_vec(LookupPack pack, int ntables
 // and consecutive workgroups of one XCD cycle through its stripes, mixing HBM-bound
 // and L2-bound work in time.
 constexpr int kXcds = 8;
+static_assert(kXcds == et_order::kXcds && ET_MAX_TABLES_PER_LAUNCH == et_order::kMaxTables,
+              "et_lookup_order.h");
 
 // 32-bit entries (table | stripe << 8) so the map is read with scalar loads (gfx950
 // has no scalar byte loads).
-constexpr int kMaxStripeEntries = 40;  // per XCD (kernel-argument size bound)
+constexpr int kMaxStripeEntries = et_order::kMaxEntries;  // per XCD
 struct StripeMap {
     // entry[x][k]: table (bits 0-7), stripe (8-15); every XCD has one entry per table
     uint32_t entry[kXcds][kMaxStripeEntries];
@@ -525,6 +528,9 @@ struct StripeMap {
     // queue per XCD), 1 = policy A (fab_share sixteenths of the CUs prefer the fabric class)
     int affinity;
     int fab_share;
+    // item order within each class queue (0 fabric, 1 cache; et_lookup_order.h), all zero = the
+    // static order; the entries of each class are listed in the order it runs them
+    et_order::ClassOrder order[2];
 };
 
 template <typename T, typename A, int D, int U, bool NT, bool SG>
@@ -631,11 +637,25 @@ __global__ __launch_bounds__(256) void k_pooled_vec_striped(LookupPack pack, Str
 //   cache-preferring:   cache(x), fabric(x), fabric(other XCDs), cache(other XCDs)
 //   fabric-preferring:  fabric(x), fabric(other XCDs), cache(x), cache(other XCDs)
 // (a cache item run on a foreign XCD misses that XCD's L2 and adds fabric bytes; a fabric item
-// costs the same anywhere, so foreign cache items come last).  Within a class the items keep
-// the static order (class slot h -> j = h / n_class, k = h % n_class).  Every workgroup tries
-// all 16 heads before giving up, heads only grow, and the grid has exactly as many workgroups
-// as items, so a workgroup that found every head exhausted would mean more than `items`
-// claims succeeded — impossible: every workgroup finds one, and none ever waits for another.
+// costs the same anywhere, so foreign cache items come last).  Every workgroup tries
+// all 16 heads before giving up, heads only grow, each class slot h < n_class * stripe_chunks
+// of XCD x is a distinct item of x (et_lookup_order.h: a bijection, checked on the host by
+// tests/lookup_order_host.cpp) and the grid has exactly as many workgroups as items, so a
+// workgroup that found every head exhausted would mean more than `items` claims succeeded —
+// impossible: every workgroup finds one, and none ever waits for another.
+//
+// Item order within a class (sm.order, DESIGN §4 "L2 order").  The static order is tables
+// fastest (class slot h -> j = h / n_class, k = h % n_class): all of a class's tables stream
+// through the XCD's L2 together.  Both classes now run TABLE-MAJOR (k = h / stripe_chunks,
+// j = h % stripe_chunks) in the order the host lists the class's entries (build_stripe_map):
+//   cache class:  the XCD's largest light table first, so all its cache workgroups touch one
+//     table at a time (twice the touch rate per line against whatever the fabric CUs stream
+//     through the same L2);
+//   fabric class: one table's stripe at a time, the list rotated by XCD, so an XCD's L2 sees one
+//     allocating stream instead of five (the 6-8 MB tables then hit in L2) while the chip as a
+//     whole still mixes HBM-bound and Infinity-Cache-bound tables at every moment.
+// Only the order of claims changes: the slot handed to striped_body is j * ntables + k as before.
+// The two-phase orders the sweep rejected exist in experiment builds only (ET_ORDER_FAB).
 // Without a policy (affinity 0: a class is empty, or fab_share 0) head[x][0] is the one queue of
 // XCD x over all its items, exactly the schedule described above.
 //   policy A (the default, fab_share 8): a workgroup prefers the fabric class iff a fixed hash
@@ -660,26 +680,28 @@ __device__ __forceinline__ uint32_t cu_hash16(uint32_t hw) {
     return ((v & 1u) << 3) | ((v & 2u) << 1) | ((v & 4u) >> 1) | ((v & 8u) >> 3);
 }
 
-// One claim from class c of XCD x: the item (x * per + its slot in the static order) or ~0u.
-__device__ __forceinline__ uint32_t claim_class(XcdQueue& q, uint32_t x, uint32_t c,
-                                                uint32_t nheavy, uint32_t ntables, uint32_t sc) {
-    const uint32_t nk = c ? ntables - nheavy : nheavy;
+// One claim from class c of XCD x: the item (x * per + the slot of class slot h, et_lookup_order.h)
+// or ~0u.
+__device__ __forceinline__ uint32_t claim_class(XcdQueue& q, const StripeMap& sm, uint32_t x,
+                                                uint32_t c, uint32_t nheavy, uint32_t ntables,
+                                                uint32_t sc) {
     const uint32_t h = atomicAdd(&q.head[x][c], 1u);
-    if (h >= nk * sc) return ~0u;
-    return x * (ntables * sc) + (h / nk) * ntables + (c ? nheavy : 0u) + h % nk;
+    const uint32_t slot = et_order::class_slot(sm.order[c], x, c, h, nheavy, ntables, sc);
+    return slot == et_order::kNone ? ~0u : x * (ntables * sc) + slot;
 }
 
 // The claim order above for a workgroup on XCD x0 that prefers class p.
-__device__ __forceinline__ uint32_t claim_pref(XcdQueue& q, uint32_t x0, uint32_t p,
-                                               uint32_t nheavy, uint32_t ntables, uint32_t sc) {
+__device__ __forceinline__ uint32_t claim_pref(XcdQueue& q, const StripeMap& sm, uint32_t x0,
+                                               uint32_t p, uint32_t nheavy, uint32_t ntables,
+                                               uint32_t sc) {
     constexpr uint32_t M = (uint32_t)(kXcds - 1);
-    uint32_t it = claim_class(q, x0, p, nheavy, ntables, sc);
-    if (it == ~0u && p == 1u) it = claim_class(q, x0, 0u, nheavy, ntables, sc);
+    uint32_t it = claim_class(q, sm, x0, p, nheavy, ntables, sc);
+    if (it == ~0u && p == 1u) it = claim_class(q, sm, x0, 0u, nheavy, ntables, sc);
     for (uint32_t k = 1; it == ~0u && k < (uint32_t)kXcds; ++k)
-        it = claim_class(q, (x0 + k) & M, 0u, nheavy, ntables, sc);
-    if (it == ~0u && p == 0u) it = claim_class(q, x0, 1u, nheavy, ntables, sc);
+        it = claim_class(q, sm, (x0 + k) & M, 0u, nheavy, ntables, sc);
+    if (it == ~0u && p == 0u) it = claim_class(q, sm, x0, 1u, nheavy, ntables, sc);
     for (uint32_t k = 1; it == ~0u && k < (uint32_t)kXcds; ++k)
-        it = claim_class(q, (x0 + k) & M, 1u, nheavy, ntables, sc);
+        it = claim_class(q, sm, (x0 + k) & M, 1u, nheavy, ntables, sc);
     return it;
 }
 
@@ -703,7 +725,7 @@ __global__ __launch_bounds__(256) void k_pooled_vec_queued(LookupPack pack, Stri
             uint32_t hw;
             asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
             const uint32_t p = cu_hash16(hw) < (uint32_t)sm.fab_share ? 0u : 1u;  // policy A
-            it = claim_pref(q, x0, p, nh, (uint32_t)ntables, sc);
+            it = claim_pref(q, sm, x0, p, nh, (uint32_t)ntables, sc);
         } else
         for (uint32_t k = 0; k < (uint32_t)kXcds; ++k) {
             const uint32_t x = (xcc + k) & (uint32_t)(kXcds - 1);
@@ -717,7 +739,7 @@ __global__ __launch_bounds__(256) void k_pooled_vec_queued(LookupPack pack, Stri
     }
     __syncthreads();
     const uint32_t it = s_item;
-    // the class queues keep the static order within each class (claim_class)
+    // the class queues only permute the items (claim_class): the slot numbering is the static one
     if (it != ~0u)
         striped_body<T, A, D, U, NT, SG>(pack, sm, ntables, batch, dst, ld_dst, rounds,
                                          stripe_chunks, nchunks, (int)(it / per),
@@ -966,6 +988,12 @@ struct LookupTuning {
     // preference)
     int affinity = 1;              // policy A
     int fab_share = 8;             // the sweep's choice (profiles/r07/cu_affinity/sweep.txt)
+    // Item order within the class queues (et_lookup_order.h, DESIGN section 4 "L2 order"):
+    // ET_ORDER_CACHE=1 cache class table-major, ET_ORDER_FAB=1|2|3 fabric class in two phases /
+    // two phases with the allocating one table-major / all table-major, ET_PHASE_BYTES the
+    // cache-class footprint above which an XCD runs its non-temporal phase first.  The sweep's
+    // choice (profiles/r08/l2_order/sweep.txt): both classes table-major
+    et_order::Policy order = {1, 3, 1 << 20};
 };
 
 inline const LookupTuning& tuning() {
@@ -985,6 +1013,9 @@ inline const LookupTuning& tuning() {
         v.heavy_prio = (int)ET_KNOB("ET_HEAVY_PRIO", v.heavy_prio);
         if (const char* e = getenv("ET_AFFINITY")) v.affinity = *e == 'A' ? 1 : 0;
         v.fab_share = (int)ET_KNOB("ET_FAB_SHARE", v.fab_share);
+        v.order.cache_major = (int)ET_KNOB("ET_ORDER_CACHE", v.order.cache_major);
+        v.order.fab = (int)ET_KNOB("ET_ORDER_FAB", v.order.fab);
+        v.order.phase_bytes = ET_KNOB("ET_PHASE_BYTES", v.order.phase_bytes);
 #endif
         return v;
     }();
@@ -993,50 +1024,33 @@ inline const LookupTuning& tuning() {
 
 int max_rounds() { return tuning().max_rounds; }
 
-// Stripe assignment: heavy tables -> stripe x on XCD x; light tables' stripes laid out
-// table after table (alternating large and small tables) and cut into kXcds equal runs.
-inline void build_stripe_map(const LookupPack& pack, int n, int es, StripeMap& sm) {
+// Stripe assignment (et_order::place_stripes) and, for the class queues, the order in which
+// each class lists its entries (et_order::order_xcd).
+inline void build_stripe_map(const LookupPack& pack, int n, int es, bool queued, StripeMap& sm) {
     const LookupTuning& tu = tuning();
-    int heavy[ET_MAX_TABLES_PER_LAUNCH], light[ET_MAX_TABLES_PER_LAUNCH];
-    int nh = 0, nl = 0;
     int64_t bytes[ET_MAX_TABLES_PER_LAUNCH];
     sm.ntload_mask = 0;
     sm.prio_mask = 0;
     for (int t = 0; t < n; ++t) {
         bytes[t] = pack.d[t].nrows * pack.d[t].ld_table * es;
         if (bytes[t] > tu.light_bytes) {
-            heavy[nh++] = t;
             if (tu.heavy_prio) sm.prio_mask |= 1u << t;
             if (tu.ntload && bytes[t] > tu.ntload_bytes) sm.ntload_mask |= 1u << t;
-        } else {
-            light[nl++] = t;
         }
     }
-    // light tables by size, then interleave large / small
-    for (int a = 0; a < nl; ++a)
-        for (int b = a + 1; b < nl; ++b)
-            if (bytes[light[b]] > bytes[light[a]]) {
-                int tmp = light[a];
-                light[a] = light[b];
-                light[b] = tmp;
-            }
-    int order[ET_MAX_TABLES_PER_LAUNCH];
-    for (int i = 0, lo = 0, hi = nl - 1; i < nl; ++i) order[i] = (i & 1) ? light[hi--] : light[lo++];
-    int cnt[kXcds] = {0};
-    for (int x = 0; x < kXcds; ++x)
-        for (int h = 0; h < nh; ++h) sm.entry[x][cnt[x]++] = (uint32_t)heavy[h] | ((uint32_t)x << 8);
-    sm.nheavy = nh;
-    // linear list of light stripes (order[i], st), st < kXcds; XCD x takes [x*nl, (x+1)*nl)
-    for (int q = 0; q < nl * kXcds; ++q) {
-        const int x = q / (nl > 0 ? nl : 1);
-        sm.entry[x][cnt[x]++] = (uint32_t)order[q / kXcds] | ((uint32_t)(q % kXcds) << 8);
-    }
-    sm.nent = cnt[0];
+    sm.nent = et_order::place_stripes(bytes, n, tu.light_bytes, sm.entry, &sm.nheavy);
     // a class preference needs both classes and a share to prefer by: otherwise none, the
     // one-queue schedule
     sm.affinity = sm.nheavy > 0 && sm.nheavy < sm.nent ? tu.affinity : 0;
     sm.fab_share = tu.fab_share < 0 ? 0 : tu.fab_share > 16 ? 16 : tu.fab_share;
     if (sm.fab_share == 0) sm.affinity = 0;
+    // the class queues' item order (only they have one: the one-queue schedule and the static
+    // kernel keep the static order, so for them the entries stay as placed)
+    memset(sm.order, 0, sizeof(sm.order));
+    if (queued && sm.affinity != 0)
+        for (int x = 0; x < kXcds; ++x)
+            et_order::order_xcd(sm.entry[x], x, sm.nent, sm.nheavy, bytes, sm.ntload_mask, tu.order,
+                                sm.order);
 }
 
 // One pooled launch: the schedule (per-XCD queues, static stripes or the linear grid) and the
@@ -1057,13 +1071,13 @@ int launch_pooled_vec(const LookupPack& pack, int n, int64_t batch, void* dst, i
     const bool striped = !PG && !MK && n > 1 && tuning().striped;
     StripeMap sm;
     int64_t stripe_chunks = 0, grid = nchunks * n;
+    const bool queued = striped && pack.queue && tuning().queued;
     if (striped) {
-        build_stripe_map(pack, n, (int)sizeof(T), sm);
+        build_stripe_map(pack, n, (int)sizeof(T), queued, sm);
         stripe_chunks = (nchunks + kXcds - 1) / kXcds;
         grid = (int64_t)kXcds * sm.nent * stripe_chunks;
     }
     if (grid > 0x7fffffffll) return fail(ET_ERR_ARG, "grid too large");
-    const bool queued = striped && pack.queue && tuning().queued;
     // `loop` is std::true_type for the scalar-addressed loop (instantiated for kSG only)
     auto launch = [&](auto loop) -> int {
         constexpr bool SG = decltype(loop)::value;

@@ -5,6 +5,8 @@ heavy (> 256 MiB), mid (4 MiB .. 256 MiB), light (<= 4 MiB), or all — and runs
 Preallocation launch (et.maplookup_) `steps` times after a warm-up, so rocprofv3 --pmc sees
 only those dispatches (tools/gpu_run.sh classpmc step; tools/traffic.py sums per dispatch).
 Prints the class's kernel time (HIP events) as one JSON line.
+CLASS may also be without:R1,R2,.. (every table but those with these row counts) or
+rows:R1,R2,.. (only those), for attributing traffic to single tables.
 Usage: python tools/class_pmc.py CLASS [steps]"""
 import json
 import os
@@ -34,7 +36,13 @@ def main():
     tids = list(range(len(bench.CRITEO_KAGGLE_ROWS)))
     tables = bench.make_tables(et, L, tids, dev)
     idx = bench.make_indices(L, tids, bench.BATCH, dev)
-    sel = [k for k in tids if PICK[cls](bench.CRITEO_KAGGLE_ROWS[k] * bench.DIM * 4)]
+    if ":" in cls:
+        kind, _, lst = cls.partition(":")
+        named = {int(r) for r in lst.split(",")}
+        assert kind in ("without", "rows") and named <= set(bench.CRITEO_KAGGLE_ROWS), cls
+        sel = [k for k in tids if (bench.CRITEO_KAGGLE_ROWS[k] in named) == (kind == "rows")]
+    else:
+        sel = [k for k in tids if PICK[cls](bench.CRITEO_KAGGLE_ROWS[k] * bench.DIM * 4)]
     tabs, ids = [tables[k] for k in sel], [idx[k] for k in sel]
     dst = torch.empty((bench.BATCH, bench.DIM * len(sel)), dtype=torch.float32, device=dev)
     strat = et.PreallocationStrategy(0)

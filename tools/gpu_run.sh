@@ -13,6 +13,8 @@
 #   exact            kernel trace of one exact config-4 update + its timeline
 #   cfg2             config 2: kernel trace (graph and eager: duration vs gap) + PMC traffic
 #   classpmc         PMC traffic + time of each headline table class alone (tools/class_pmc.py)
+#   pmc1:CLASS[:LIB[:VAR=V,..]]  PMC traffic + time of one tools/class_pmc.py table set (heavy, all,
+#                    without:R1,R2 ...) with the shipped library or library path LIB and env VAR=V
 #   lookab:LIB:S1/S2:N  the headline launch (kernel ms) with library LIB and env sets S1, S2
 #                    (VAR=V,VAR=V; NONE=0 for none), alternating N times; a set LIB=NAME[,VAR=V..]
 #                    runs with tools/alt/libembtab_hip_NAME.so; lookab:LIB:SETS:N:STEPS sets --steps
@@ -109,6 +111,25 @@ print('bench', round(d['ms_per_step'],4), 'ms frac', round(d['roofline']['frac']
 print('$SETS $c', t['tables'], 'tables', round(t['ms_median'],4), 'ms', 'fabric', round(d.get('hbm_bytes_per_launch',0)/1e9,3), 'GB', \
 'compulsory', round(t['hbm_compulsory_bytes']/1e9,3), 'GB', 'alg', round(t['algorithmic_bytes']/1e9,3), 'GB', 'L2hit', round(d.get('l2_hit_rate',0),3))"
       done ;;
+    pmc1:*)
+      IFS=: read -r _ K1 K2 REST <<< "$step"
+      # CLASS itself may hold one colon (without:R1,R2)
+      case "$K1" in without|rows) c="$K1:$K2"; IFS=: read -r LIBV SETS <<< "$REST" ;; *) c=$K1; LIBV=$K2; SETS=$REST ;; esac
+      D=$OUT/pmc1_$(echo "$c" | tr ':,' '__')$([ -n "$LIBV" ] && echo "_$(basename "$LIBV" .so)")$([ -n "$SETS" ] && echo "_$(echo "$SETS" | tr ',=' '__')")
+      mkdir -p "$D"
+      env ET_LIBRARY=$LIBV $(echo "${SETS:-NONE=0}" | tr ',' ' ') timeout -k 10 120 python3 tools/class_pmc.py $c 10 \
+        > "$D/time.json" 2> "$D/time.err" || die pmc1 "$D/time.err"
+      for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
+        tag=$(echo "$grp" | tr ' ' '_')
+        env ET_LIBRARY=$LIBV $(echo "${SETS:-NONE=0}" | tr ',' ' ') timeout -s KILL 100 rocprofv3 --pmc $grp -d "$D/$tag" -o run --output-format csv \
+          -- python3 tools/class_pmc.py $c 5 > "$D/$tag.log" 2>&1 || die "pmc1 $c $tag" "$D/$tag.log"
+      done
+      python3 tools/traffic.py "$D" k_pooled_vec "set_$c" "$D/traffic.json" > /dev/null
+      rm -rf "$D"/FETCH_SIZE "$D"/WRITE_SIZE "$D"/TCC_HIT_sum_TCC_MISS_sum
+      python3 -c "import json; t=json.load(open('$D/time.json')); d=json.load(open('$D/traffic.json')); \
+print('pmc1 $c $LIBV $SETS', t['tables'], 'tables', round(t['ms_median'],4), 'ms', 'fabric', round(d.get('hbm_bytes_per_launch',0)/1e9,3), 'GB', \
+'read', round(d.get('read_bytes_per_launch',0)/1e9,3), 'compulsory', round(t['hbm_compulsory_bytes']/1e9,3), 'GB', 'L2hit', round(d.get('l2_hit_rate',0),3))" \
+        | tee -a "$OUT/pmc1.txt" ;;
     cfg2)
       D=$OUT/cfg2; mkdir -p "$D"
       for m in graph eager; do

@@ -6,7 +6,9 @@ Every workgroup of the striped or the queued kernel stamps its start and end (s_
 classes share a CU (cu_affinity below).  Reported per XCC and per table class (heavy:
 > 256 MiB, mid: > 4 MiB, light): when the class's workgroups start and end, so one can
 see whether the L2-bound light stripes run after the heavy stripes have drained (the
-launch's tail) or beside them.  Usage (GPU box): python tools/wg_timeline.py OUT.json"""
+launch's tail) or beside them, and per table ("per_table": mean workgroup duration, first start,
+last end).  ET_TL_CLASS=light|mid|heavy runs that class's tables alone (tools/class_pmc.py PICK).
+Usage (GPU box): python tools/wg_timeline.py OUT.json"""
 import ctypes
 import json
 import os
@@ -107,6 +109,12 @@ def main():
     tids = list(range(len(bench.CRITEO_KAGGLE_ROWS)))
     tables = bench.make_tables(et, L, tids, dev)
     idx = bench.make_indices(L, tids, bench.BATCH, dev)
+    if os.environ.get("ET_TL_CLASS"):
+        from class_pmc import PICK
+        keep = [k for k in tids if PICK[os.environ["ET_TL_CLASS"]](bench.CRITEO_KAGGLE_ROWS[k] * bench.DIM * 4)]
+        tables, idx = [tables[k] for k in keep], [idx[k] for k in keep]
+        bench.CRITEO_KAGGLE_ROWS[:] = [bench.CRITEO_KAGGLE_ROWS[k] for k in keep]
+        tids = list(range(len(keep)))
     strat = et.PreallocationStrategy(0)
     dst = torch.empty((bench.BATCH, bench.DIM * len(tids)), dtype=torch.float32, device=dev)
     runs = []
@@ -170,6 +178,15 @@ def main():
                 lo, hi = max(a, q * 50.0), min(b, (q + 1) * 50.0)
                 if hi > lo:
                     prof[k][q] += (hi - lo) / 50.0
+    out["per_table"] = {}
+    for t in tids:
+        m = tab == t
+        if m.any():
+            d = e[m] - s[m]
+            out["per_table"][str(rows[t])] = {
+                "class": cls(t), "workgroups": int(m.sum()), "wg_us_mean": round(float(d.mean()), 2),
+                "wg_us_p90": round(float(np.percentile(d, 90)), 2),
+                "first_start_us": round(float(s[m].min()), 1), "last_end_us": round(float(e[m].max()), 1)}
     out["resident_wg_per_50us"] = {k: [round(v, 1) for v in p] for k, p in prof.items()}
     out["cu_affinity"] = cu_affinity(s, e, c, xcc, hw, home, fab_share)
     out["xcc_of_blockIdx_mod8_agrees"] = float(np.mean((np.arange(grid) % 8) == xcc))
