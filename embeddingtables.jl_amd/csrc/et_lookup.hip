@@ -1519,6 +1519,9 @@ extern "C" int et_ragged_maplookup_prealloc(int dtype, const et_ragged_desc* des
 
 ET_OOB_READER(lookup)
 
+// Row-wise quantised tables (et_quantize_rows, et_quant_maplookup_prealloc).
+#include "et_quant.hip"
+
 #ifdef ET_WG_TIMELINE
 // Profiling build only: copies the striped launch's workgroup records (2 x uint4 each)
 // to host memory; returns the number copied.

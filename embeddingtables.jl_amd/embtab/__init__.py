@@ -12,6 +12,7 @@ from .tables import (AbstractEmbeddingTable, AbstractLookupType, ArgumentError, 
                      Forward, IndexingContext, NoContext, SimpleEmbedding, SplitEmbedding, Static,
                      Update, columnpointer, example, featuresize)
 from .ragged import RaggedIndices
+from .quant import QuantizedEmbedding
 from .lookup import (AbstractExecutionStrategy, DefaultStrategy, NoTangent,
                      PreallocationPlan, PreallocationStrategy, SimpleParallelStrategy, colwrap, destination, lookup,
                      lookup_, maplookup, maplookup_)
@@ -30,5 +31,5 @@ __all__ = [
     "rrule", "Descent", "AbstractIndexer", "Indexer", "SparseIndexer", "DenseIndexer",
     "IndexerView", "index_", "gettranslations", "update_", "optimise_update_",
     "ensemble_update", "PhasedUpdate", "EmbtabError", "check_errors",
-    "RaggedIndices", "AdaGrad",
+    "RaggedIndices", "AdaGrad", "QuantizedEmbedding",
 ]

@@ -71,6 +71,8 @@ EXPORTS = (
     "et_ragged_sgd",
     "et_adagrad_workspace_size",
     "et_sparse_adagrad",
+    "et_quantize_rows",
+    "et_quant_maplookup_prealloc",
     "et_concat_slabs",
     "et_split_slabs",
     "et_push_cols",
@@ -202,6 +204,26 @@ class AdaGradDesc(ctypes.Structure):
     ]
 
 
+class QuantDesc(ctypes.Structure):
+    """et_quant_desc (include/embtab.h)."""
+
+    _fields_ = [
+        ("table", ctypes.c_void_p),
+        ("ld_bytes", ctypes.c_int64),
+        ("nrows", ctypes.c_int64),
+        ("dim", ctypes.c_int32),
+        ("bits", ctypes.c_int32),
+        ("hdr", ctypes.c_void_p),
+        ("pool", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("idx", ctypes.c_void_p),
+        ("ld_idx", ctypes.c_int64),
+        ("colptr", ctypes.c_void_p),
+        ("nnz", ctypes.c_int64),
+        ("dst_row_off", ctypes.c_int64),
+    ]
+
+
 _lib = None
 
 
@@ -246,6 +268,8 @@ def load() -> ctypes.CDLL:
         "et_ragged_sgd": ([c_int, vp, i32, dbl, u32, vp, i64, vp], c_int),
         "et_adagrad_workspace_size": ([vp, i32, vp], c_int),
         "et_sparse_adagrad": ([c_int, vp, i32, dbl, dbl, u32, vp, i64, vp], c_int),
+        "et_quantize_rows": ([vp, i64, i64, i32, i32, vp, i64, vp, vp], c_int),
+        "et_quant_maplookup_prealloc": ([c_int, vp, i32, i64, vp, i64, u32, vp], c_int),
         "et_concat_slabs": ([c_int, vp, i32, i64, i64, vp, vp, vp, i64, vp], c_int),
         "et_split_slabs": ([c_int, vp, i64, i64, i32, vp, vp, vp, i64, vp], c_int),
         "et_push_cols": ([c_int, vp, i64, i64, i64, i64, vp, i32, vp], c_int),

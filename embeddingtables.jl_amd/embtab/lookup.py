@@ -20,6 +20,7 @@ import threading
 import torch
 
 from . import _lib
+from .quant import QuantizedEmbedding, is_quantized_list, quant_descs, quant_launch
 from .ragged import RaggedIndices, arithmetic_colptr
 from .tables import AbstractEmbeddingTable, ArgumentError, featuresize, example
 
@@ -101,7 +102,11 @@ def _ld(x: torch.Tensor) -> int:
 def _check_dst(dst: torch.Tensor, A, B: int):
     if not isinstance(dst, torch.Tensor) or dst.dim() != 2:
         raise ArgumentError("destination must be a 2-D (B, D) tensor")
-    if dst.dtype != A.dtype:
+    if isinstance(A, QuantizedEmbedding):  # dequantised sums: Float32, or rounded once to 16 bits
+        if dst.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise ArgumentError(f"destination eltype {dst.dtype} of a quantised lookup is not "
+                                "Float32, Float16 or BFloat16")
+    elif dst.dtype != A.dtype:
         raise ArgumentError(f"destination eltype {dst.dtype} != table eltype {A.dtype}")
     if dst.shape[0] != B or dst.shape[1] != featuresize(A):
         raise ArgumentError(f"destination shape {tuple(dst.shape)} != ({B}, {featuresize(A)})")
@@ -143,6 +148,9 @@ def lookup_(dst: torch.Tensor, A: AbstractEmbeddingTable, I: torch.Tensor,
     L = _lib.load()
     D, R = A.size()
     flags = _lib.ET_FLAG_NONTEMPORAL if nontemporal else 0
+    if isinstance(A, QuantizedEmbedding):  # one et_quant_maplookup_prealloc launch
+        quant_launch(quant_descs([A], [I], B, 0), 1, B, dst, _ld(dst), flags)
+        return dst
     table, cpp = A.device_table()
     if isinstance(I, RaggedIndices):
         # variable-length bags: the ragged entry point with one table
@@ -340,6 +348,18 @@ class PreallocationPlan:
         if k + sum(featuresize(t) for t in tables) > dst.shape[1]:
             raise ArgumentError("destination has too few rows for prependrows + sum(D)")
         dtype = tables[0].dtype  # the tables' element type; dst may be another (U)
+        self._quant = is_quantized_list(tables)  # all quantised, or none (a mix raises)
+        if self._quant:  # fixed-pool and ragged indices alike: et_quant_maplookup_prealloc
+            if f16_fp32_acc:
+                raise ArgumentError("f16_fp32_acc belongs to Float16 tables: a quantised lookup "
+                                    "always sums in Float32")
+            self._keep = (dst, tables, Is)
+            self._descs = quant_descs(tables, Is, B, k)
+            self._n, self._B = len(tables), B
+            self._flags = _lib.ET_FLAG_NONTEMPORAL if nontemporal else 0
+            self._dst, self._ld = dst, _ld(dst)
+            _lib.et_dtype(dst)
+            return
         self._ragged = any(isinstance(i, RaggedIndices) for i in Is)
         if self._ragged and dst.dtype != dtype:
             raise NotImplementedError(
@@ -365,6 +385,9 @@ class PreallocationPlan:
     def __call__(self):
         """Launch on the current stream; returns the destination."""
         dst = self._dst
+        if self._quant:
+            quant_launch(self._descs, self._n, self._B, dst, self._ld, self._flags)
+            return dst
         stream = _lib.stream_handle(dst.device)
         if self._ragged:
             _lib.check(self._lib.et_ragged_maplookup_prealloc(

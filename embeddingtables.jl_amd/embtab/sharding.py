@@ -34,6 +34,7 @@ import torch
 
 from . import _lib
 from .lookup import _ld
+from .quant import refuse as refuse_quantized
 
 VEC_DIMS = (512, 256, 128, 64, 32, 16)  # the vector kernels' feature widths
 
@@ -161,6 +162,7 @@ def piece_table(full, piece: Piece):
     reference's update dispatch of the parent (fused iff the parent is)."""
     from .tables import Dynamic, SimpleEmbedding, Static, fused_update_path
 
+    refuse_quantized(full, "piece_table")
     D = full.size()[0]
     if piece.f0 == 0 and piece.dim == D:
         return full
@@ -176,6 +178,7 @@ def compact_piece_table(full, piece: Piece):
     pieces return the table itself.  Same update dispatch as the parent."""
     from .tables import Dynamic, SimpleEmbedding, Static, fused_update_path
 
+    refuse_quantized(full, "compact_piece_table")
     D = full.size()[0]
     if piece.f0 == 0 and piece.dim == D:
         return full
@@ -482,6 +485,7 @@ class ShardedMapLookup:
     def __call__(self, piece_tables, piece_idx, dst: torch.Tensor) -> torch.Tensor:
         """Run the sharded step; ``dst`` is ``(B, k + sum D)`` (allgather) or this
         rank's ``(B_r, k + sum D)`` batch slice (alltoall); p2p returns ``self.out``."""
+        refuse_quantized(piece_tables, type(self).__name__)
         if self._native is not None:
             return self._native(piece_tables, piece_idx, dst)
         if self.exchange_kind == "p2p":
@@ -645,6 +649,7 @@ class NativeShardedStep:
         return self._descs[key]
 
     def __call__(self, piece_tables, piece_idx, dst):
+        refuse_quantized(piece_tables, type(self).__name__)
         descs, n, _ = self._local_descs(piece_tables, piece_idx)
         _lib.check(self.L.et_sharded_maplookup(
             self.h, ctypes.addressof(descs), n, dst.data_ptr(), _ld(dst),

@@ -22,6 +22,7 @@ import torch
 from . import _lib
 from .lookup import (NoTangent, PreallocationStrategy, AbstractExecutionStrategy, colwrap,
                      lookup, maplookup, _ld, _check_idx)
+from .quant import refuse as refuse_quantized
 from .ragged import RaggedIndices
 from .tables import (AbstractEmbeddingTable, AbstractLookupType, ArgumentError, Dynamic,
                      featuresize, fused_update_path)
@@ -79,6 +80,7 @@ def rrule(f, *args):
     ``(y, pullback)``; the pullback returns ``SparseEmbeddingUpdate``s."""
     if f is lookup:
         A, I = args
+        refuse_quantized(A, "rrule")
         S = A.lookup_type
         y = lookup(A, I)
 
@@ -89,6 +91,7 @@ def rrule(f, *args):
     if f is maplookup:
         strategy, tables, I = args
         tables = list(tables)
+        refuse_quantized(tables, "rrule")
         Is = colwrap(I)
         y = maplookup(strategy, tables, I)
         if isinstance(strategy, PreallocationStrategy):
@@ -516,6 +519,9 @@ def update_(*args, nontemporal: bool | None = None, exact: bool | None = None,
       one call per element type and at most ET_MAX_TABLES_PER_LAUNCH tables.  ``nontemporal``
       is its only keyword: ``exact``, ``hot_pass``, ``f16_fp32_acc``, ``indexer`` /
       ``indexers`` and ``telemetry_cb`` belong to the SGD and raise ``ArgumentError``."""
+    for a in args[:2]:  # the table(s): first or second argument in every form
+        if isinstance(a, (AbstractEmbeddingTable, list, tuple)):
+            refuse_quantized(a, "update_")
     if args and isinstance(args[0], AdaGrad):
         refused = {"exact": exact is not None, "f16_fp32_acc": bool(f16_fp32_acc),
                    "hot_pass": bool(hot_pass), "indexer / indexers (positional)": len(args) > 3}
@@ -786,6 +792,7 @@ class PhasedUpdate:
         if exact is None:
             exact = EXACT_DEFAULT
         tables, grads = list(tables), list(grads)
+        refuse_quantized(tables, "PhasedUpdate")
         if len(tables) != len(grads):
             raise ArgumentError("tables and grads differ in length")
         if any(isinstance(g.indices, RaggedIndices) for g in grads):

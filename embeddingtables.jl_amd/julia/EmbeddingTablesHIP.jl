@@ -24,6 +24,7 @@ const libhip = "libamdhip64.so"
 
 const ET_F32, ET_F16, ET_F64, ET_I32, ET_I64 = Cint(0), Cint(1), Cint(2), Cint(3), Cint(4)
 const ET_FLAG_NONTEMPORAL = UInt32(1)
+const ET_MAX_TABLES_PER_LAUNCH = 32          # include/embtab.h
 const ET_FLAG_EXACT_UPDATE = UInt32(4)      # every column summed serially (bit-identical)
 const ET_FLAG_EXACT_IF_FAST = UInt32(256)   # the default: exact (ABI v9: every eltype and size)
 const ET_FLAG_SGD_UNFUSED = UInt32(8)
@@ -654,6 +655,96 @@ function maplookup!(strategy::PreallocationStrategy, dst::HipMatrix{T},
     return dst
 end
 
+#####
+##### Row-wise quantised tables (inference only; include/embtab.h "Row-wise quantised tables"):
+##### INT8 / INT4 rows with a Float16 scale and bias per row, dequantised inside the pooled sum.
+##### `packed` is ld_bytes x R (column r = row r of the format: payload, then the fused header);
+##### `header` is a 4 x R UInt8 array for the split form.  No counterpart in the reference.
+#####
+
+struct QuantDesc
+    table::Ptr{Cvoid}
+    ld_bytes::Int64
+    nrows::Int64
+    dim::Int32
+    bits::Int32
+    hdr::Ptr{Cvoid}
+    pool::Int32
+    reserved::Int32
+    idx::Ptr{Int64}
+    ld_idx::Int64
+    colptr::Ptr{Int64}
+    nnz::Int64
+    dst_row_off::Int64
+end
+
+struct QuantizedEmbedding
+    packed::HipMatrix{UInt8}
+    dim::Int
+    bits::Int
+    header::Union{Nothing,HipMatrix{UInt8}}
+end
+EmbeddingTables.featuresize(Q::QuantizedEmbedding) = Q.dim
+Base.size(Q::QuantizedEmbedding) = (Q.dim, size(Q.packed, 2))
+
+# Quantise a dense Float32 D x R device matrix (et_quantize_rows); ld_bytes defaults to the
+# payload (+ 4 when fused) rounded up to 16.
+function QuantizedEmbedding(src::HipMatrix{Float32}; bits::Integer = 8, split_header::Bool = false,
+                            ld_bytes::Integer = cld(size(src, 1) * bits ÷ 8 +
+                                                    (split_header ? 0 : 4), 16) * 16)
+    D, R = size(src)
+    packed = HipArray{UInt8}(undef, ld_bytes, R)
+    ccall((:hipMemset, libhip), Cint, (Ptr{Cvoid}, Cint, Csize_t), packed.ptr, 0, ld_bytes * R)
+    header = split_header ? HipArray{UInt8}(undef, 4, R) : nothing
+    check(ccall((:et_quantize_rows, libembtab), Cint,
+                (Ptr{Float32}, Int64, Int64, Int32, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                src.ptr, leading(src), R, D, bits, packed.ptr, ld_bytes,
+                header === nothing ? C_NULL : header.ptr, stream()))
+    return QuantizedEmbedding(packed, D, bits, header)
+end
+
+_quant_hdr(Q::QuantizedEmbedding) = Q.header === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(Q.header.ptr)
+_quant_desc(Q::QuantizedEmbedding, I::HipVector{Int}, off) =
+    QuantDesc(Q.packed.ptr, leading(Q.packed), size(Q.packed, 2), Q.dim, Q.bits, _quant_hdr(Q), 1, 0,
+              I.ptr, 1, C_NULL, 0, off)
+_quant_desc(Q::QuantizedEmbedding, I::HipMatrix{Int}, off) =
+    QuantDesc(Q.packed.ptr, leading(Q.packed), size(Q.packed, 2), Q.dim, Q.bits, _quant_hdr(Q),
+              size(I, 1), 0, I.ptr, leading(I), C_NULL, 0, off)
+_quant_desc(Q::QuantizedEmbedding, R::RaggedIndices, off) =
+    QuantDesc(Q.packed.ptr, leading(Q.packed), size(Q.packed, 2), Q.dim, Q.bits, _quant_hdr(Q), 0, 0,
+              R.values.ptr, 0, R.colptr.ptr, length(R.values), off)
+_quant_batch(I::HipArray) = size(I, ndims(I))
+_quant_batch(R::RaggedIndices) = batchsize(R)
+
+# dst: Float32, or Float16 (the Float32 sums rounded once)
+function _quant_maplookup(::Type{U}, descs::Vector{QuantDesc}, batch, p, ld) where {U}
+    for c in 1:ET_MAX_TABLES_PER_LAUNCH:length(descs)
+        part = descs[c:min(c + ET_MAX_TABLES_PER_LAUNCH - 1, length(descs))]
+        check(ccall((:et_quant_maplookup_prealloc, libembtab), Cint,
+                    (Cint, Ptr{QuantDesc}, Int32, Int64, Ptr{Cvoid}, Int64, UInt32, Ptr{Cvoid}),
+                    et_dtype(U), part, length(part), batch, p, ld, ET_FLAG_NONTEMPORAL, stream()))
+    end
+end
+
+function lookup!(dst, Q::QuantizedEmbedding, I::Union{HipVector{Int},HipMatrix{Int},RaggedIndices})
+    p, ld = _ptr_ld(dst)
+    _quant_maplookup(eltype(dst), [_quant_desc(Q, I, 0)], _quant_batch(I), p, ld)
+    return dst
+end
+
+# a list of only quantised tables: ONE fused launch (per 32 tables)
+function maplookup!(strategy::PreallocationStrategy, dst::HipMatrix{U},
+                    x::Vector{QuantizedEmbedding}, I::Vector; kw...) where {U}
+    descs = Vector{QuantDesc}(undef, length(x))
+    off = strategy.prependrows
+    for (t, (Q, i)) in enumerate(zip(x, I))
+        descs[t] = _quant_desc(Q, i, off)
+        off += Q.dim
+    end
+    _quant_maplookup(U, descs, _quant_batch(first(I)), dst.ptr, leading(dst))
+    return dst
+end
+
 # the gradient column (bag, 1-based) of every entry; 0 for the capacity tail
 function bag_ids(R::RaggedIndices)
     bag = HipArray{Int}(undef, length(R.values))
@@ -903,7 +994,7 @@ function maplookup!(S::ShardedPreallocation, dst::HipMatrix{T}, tables::Vector{<
     return dst
 end
 
-export HipEmbedding, HipSplitEmbedding, HipArray, HipVector, HipMatrix, EmbtabError,
+export QuantizedEmbedding, HipEmbedding, HipSplitEmbedding, HipArray, HipVector, HipMatrix, EmbtabError,
     DeviceColumns, HipIndexer, ShardedPreallocation, shard_plan, comm_id, comm_init,
     comm_destroy, comm_loopback, RaggedIndices, RaggedEmbeddingUpdate, bag_ids
 

@@ -439,6 +439,88 @@ int et_sparse_adagrad(int dtype, const et_adagrad_desc* descs, int32_t ntables, 
                       double eps, uint32_t flags, void* workspace, int64_t ws_bytes,
                       void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Row-wise quantised tables (inference only): INT8 or INT4 rows with a per-row Float16 scale
+ * and bias, dequantised inside the pooled sum — the layout of FBGEMM's Fused8BitRowwise /
+ * FusedNBitRowwise with half-precision headers.  The reference has no quantised table; the
+ * definitions here are the contract.
+ *
+ * A quantised table is `nrows` rows; row r (1-based) starts at table + (r-1)*ld_bytes.
+ *   payload  bytes [0, payload) of the row, payload = dim*bits/8.
+ *            bits = 8: feature f is byte f (unsigned).
+ *            bits = 4: dim is even; feature 2k is the low nibble of byte k, feature 2k+1 the
+ *            high nibble.
+ *   header   scale then bias, both IEEE Float16, little-endian, 4 bytes in all.
+ *            fused (hdr == NULL): bytes [payload, payload+4) of the row; ld_bytes >= payload+4.
+ *            split (hdr != NULL): hdr is a device array of nrows 4-byte headers;
+ *            ld_bytes >= payload.
+ *            In both forms ld_bytes is a multiple of 4.
+ *   reads    a kernel may read any byte of [row, row + ld_bytes); it never reads outside
+ *            nrows*ld_bytes of the table or nrows*4 of hdr, and no result depends on the
+ *            padding bytes.
+ *
+ * Dequantisation, in Float32:  v_f = float(q_f)*float(scale) + float(bias).
+ * q_f has at most 8 significant bits and a half has 11, so the product has at most 19 and is
+ * EXACT in Float32 (24): v_f carries exactly one rounding whether the expression is evaluated
+ * as a multiply and an add or as one fused multiply-add (tests/test_quant_host.py checks the
+ * product against Float64 for every q and random half scales, subnormal ones included).
+ *
+ * Quantiser, per row; every operation is one correctly rounded Float32 operation:
+ *   L = 2^bits - 1;  lo = min_f x_f;  hi = max_f x_f
+ *   bias = half_rne(lo);  b = float(bias)
+ *   scale = half_rne((hi - b) / L);  if float(scale) is not a finite value > 0: scale = 1.0
+ *   s = float(scale);  q_f = min(max(rint((x_f - b) / s), 0), L)     (rint: ties to even)
+ * A row holding a non-finite value or |x| > 65504 gets unspecified contents (never a fault);
+ * so does the sign of a zero bias when the row's minimum is attained by both -0 and +0.  The
+ * quantiser writes the payload and the header only, never the padding.
+ *
+ * Tables are contiguous only: paged quantised tables are out of scope.
+ * ------------------------------------------------------------------------------- */
+
+/* One table of a quantised lookup: fixed-pool (colptr == NULL) or ragged. */
+typedef struct et_quant_desc {
+    const void* table;     /* device pointer to row 1 */
+    int64_t ld_bytes;      /* bytes between consecutive rows (a multiple of 4) */
+    int64_t nrows;
+    int32_t dim;           /* features per row */
+    int32_t bits;          /* 8 or 4 */
+    const void* hdr;       /* NULL: header fused in the row */
+    int32_t pool;          /* fixed pool (1 = vector index); ignored when ragged */
+    int32_t reserved;      /* 0 */
+    const int64_t* idx;    /* fixed pool: bag j at idx + j*ld_idx; ragged: the values */
+    int64_t ld_idx;        /* fixed pool only */
+    const int64_t* colptr; /* NULL: a fixed pool.  Else batch + 1 entries, as et_ragged_desc */
+    int64_t nnz;           /* ragged: capacity of idx */
+    int64_t dst_row_off;   /* as in et_lookup_desc */
+} et_quant_desc;
+
+/* Quantise `nrows` rows of a contiguous Float32 source (row r at src + r*ld_src, ld_src >= dim)
+ * into a quantised table (format and arithmetic above); hdr == NULL writes fused headers.
+ * bits 8 or 4 (dim even); ld_bytes a multiple of 4 and large enough: otherwise ET_ERR_ARG. */
+int et_quantize_rows(const float* src, int64_t ld_src, int64_t nrows, int32_t dim, int32_t bits,
+                     void* table, int64_t ld_bytes, void* hdr, void* stream);
+
+/* Fused pooled lookup + concat over quantised tables.  For every table t and bag j (a fixed
+ * pool or a ragged bag, clamped and counted as et_ragged_desc's):
+ *   acc = v(first row), a COPY; acc = acc + v(next row) one row at a time in index order, in
+ *   Float32; an empty bag or pool == 0 writes +0; an index outside 1..nrows adds a zero row
+ *   and is counted (et_check_errors);
+ *   dst[desc[t].dst_row_off + (0:dim_t-1), j] = acc converted once (RNE) to dst_dtype
+ * (ET_F32, ET_F16 or ET_BF16; anything else: ET_ERR_UNSUPPORTED).  The ET_F32 result equals
+ * et_maplookup_prealloc / et_ragged_maplookup_prealloc on the dequantised Float32 table bit
+ * for bit, and the 16-bit results equal et_maplookup_prealloc_to on it.  Fixed-pool and ragged
+ * tables, INT8 and INT4, fused and split headers may share one call.  Rows that are whole
+ * 16-byte vectors (table 16-byte aligned, ld_bytes % 16 == 0, dim*bits/8 % 16 == 0, at most
+ * 1024 payload bytes) take the vector kernel, every other shape a generic one with the same
+ * results.  Flags: ET_FLAG_NONTEMPORAL (the stores); any other flag: ET_ERR_UNSUPPORTED.
+ * ET_ERR_ARG before any device work: bits not 8 or 4, an odd dim with 4 bits, ld_bytes too
+ * small or not a multiple of 4, negative sizes, ntables > ET_MAX_TABLES_PER_LAUNCH.
+ * Stream-ordered on the caller's stream only, allocates nothing, never synchronises:
+ * capturable.  batch == 0 is a no-op. */
+int et_quant_maplookup_prealloc(int dst_dtype, const et_quant_desc* descs, int32_t ntables,
+                                int64_t batch, void* dst, int64_t ld_dst, uint32_t flags,
+                                void* stream);
+
 /* Assemble the Preallocation concat from per-rank slabs after an all-gather
  * (table-wise sharding across GPUs, no counterpart in the single-process
  * reference): slab r is a (slab_ld x batch) column-major block at
