@@ -1422,6 +1422,9 @@ int lookup_dispatch_convert(int dtype, int out_dtype, const et_lookup_desc* desc
 // Variable-length bags (et_ragged_maplookup_prealloc): kernels and dispatch.
 #include "et_ragged.hip"
 
+// Weighted and mean-pooled bags (et_weighted_maplookup_prealloc, et_weighted_weight_grad).
+#include "et_weighted.hip"
+
 }  // namespace et
 
 // ---------------------------------------------------------------------------
@@ -1515,6 +1518,22 @@ extern "C" int et_ragged_maplookup_prealloc(int dtype, const et_ragged_desc* des
     et::open_side_streams(static_cast<hipStream_t>(stream));
     return et::ragged_dispatch(dtype, descs, ntables, batch, dst, ld_dst, flags,
                                static_cast<hipStream_t>(stream));
+}
+
+extern "C" int et_weighted_maplookup_prealloc(int dtype, const et_weighted_desc* descs,
+                                              int32_t ntables, int64_t batch, void* dst,
+                                              int64_t ld_dst, uint32_t flags, void* stream) {
+    et::clear_err();
+    et::open_side_streams(static_cast<hipStream_t>(stream));
+    return et::weighted_dispatch(dtype, descs, ntables, batch, dst, ld_dst, flags,
+                                 static_cast<hipStream_t>(stream));
+}
+
+extern "C" int et_weighted_weight_grad(int dtype, const et_weighted_update_desc* descs,
+                                       int32_t ntables, void* stream) {
+    et::clear_err();
+    et::open_side_streams(static_cast<hipStream_t>(stream));
+    return et::weight_grad_dispatch(dtype, descs, ntables, static_cast<hipStream_t>(stream));
 }
 
 ET_OOB_READER(lookup)

@@ -3745,6 +3745,9 @@ extern "C" int et_update_indexed(int dtype, void* table, int64_t ld_table,
 // Ragged gradients (et_ragged_sgd, et_ragged_bag_ids): kernels and entry points.
 #include "et_ragged_update.hip"
 
+// Weighted ragged gradients (et_weighted_sgd): kernel and entry points.
+#include "et_weighted_update.hip"
+
 // Sparse AdaGrad (et_sparse_adagrad): kernels and entry points.
 #include "et_adagrad.hip"
 

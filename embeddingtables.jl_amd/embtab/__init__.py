@@ -13,6 +13,7 @@ from .tables import (AbstractEmbeddingTable, AbstractLookupType, ArgumentError, 
                      Update, columnpointer, example, featuresize)
 from .ragged import RaggedIndices
 from .quant import QuantizedEmbedding
+from .weighted import WeightedIndices
 from .lookup import (AbstractExecutionStrategy, DefaultStrategy, NoTangent,
                      PreallocationPlan, PreallocationStrategy, SimpleParallelStrategy, colwrap, destination, lookup,
                      lookup_, maplookup, maplookup_)
@@ -31,5 +32,5 @@ __all__ = [
     "rrule", "Descent", "AbstractIndexer", "Indexer", "SparseIndexer", "DenseIndexer",
     "IndexerView", "index_", "gettranslations", "update_", "optimise_update_",
     "ensemble_update", "PhasedUpdate", "EmbtabError", "check_errors",
-    "RaggedIndices", "AdaGrad", "QuantizedEmbedding",
+    "RaggedIndices", "AdaGrad", "QuantizedEmbedding", "WeightedIndices",
 ]

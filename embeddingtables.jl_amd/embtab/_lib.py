@@ -32,6 +32,7 @@ ET_FLAG_SGD_INDEX_ONLY = 32
 ET_FLAG_SGD_APPLY_ONLY = 64
 ET_FLAG_SGD_HOT_PASS = 128
 ET_FLAG_ADAGRAD_ROWWISE = 512
+ET_POOL_SUM, ET_POOL_MEAN = 0, 1
 ET_MAX_TABLES_PER_LAUNCH = 32
 ET_SGD_CHUNK = 256  # include/embtab.h: occurrences per chunk of the non-exact SGD
 ET_ABI_VERSION = 9
@@ -69,6 +70,10 @@ EXPORTS = (
     "et_ragged_bag_ids",
     "et_ragged_sgd_workspace_size",
     "et_ragged_sgd",
+    "et_weighted_maplookup_prealloc",
+    "et_weighted_weight_grad",
+    "et_weighted_sgd_workspace_size",
+    "et_weighted_sgd",
     "et_adagrad_workspace_size",
     "et_sparse_adagrad",
     "et_quantize_rows",
@@ -182,6 +187,45 @@ class RaggedUpdateDesc(ctypes.Structure):
     ]
 
 
+class WeightedDesc(ctypes.Structure):
+    """et_weighted_desc (include/embtab.h)."""
+
+    _fields_ = [
+        ("table", ctypes.c_void_p),
+        ("ld_table", ctypes.c_int64),
+        ("nrows", ctypes.c_int64),
+        ("dim", ctypes.c_int32),
+        ("mode", ctypes.c_int32),
+        ("idx", ctypes.c_void_p),
+        ("nnz", ctypes.c_int64),
+        ("colptr", ctypes.c_void_p),
+        ("dst_row_off", ctypes.c_int64),
+        ("cols_per_page", ctypes.c_int64),
+        ("weights", ctypes.c_void_p),
+    ]
+
+
+class WeightedUpdateDesc(ctypes.Structure):
+    """et_weighted_update_desc (include/embtab.h)."""
+
+    _fields_ = [
+        ("table", ctypes.c_void_p),
+        ("ld_table", ctypes.c_int64),
+        ("nrows", ctypes.c_int64),
+        ("dim", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("delta", ctypes.c_void_p),
+        ("ld_delta", ctypes.c_int64),
+        ("idx", ctypes.c_void_p),
+        ("nnz", ctypes.c_int64),
+        ("colptr", ctypes.c_void_p),
+        ("batch", ctypes.c_int64),
+        ("cols_per_page", ctypes.c_int64),
+        ("weights", ctypes.c_void_p),
+        ("dweights", ctypes.c_void_p),
+    ]
+
+
 class AdaGradDesc(ctypes.Structure):
     """et_adagrad_desc (include/embtab.h)."""
 
@@ -266,6 +310,10 @@ def load() -> ctypes.CDLL:
         "et_ragged_bag_ids": ([vp, i64, i64, vp, vp], c_int),
         "et_ragged_sgd_workspace_size": ([vp, i32, vp], c_int),
         "et_ragged_sgd": ([c_int, vp, i32, dbl, u32, vp, i64, vp], c_int),
+        "et_weighted_maplookup_prealloc": ([c_int, vp, i32, i64, vp, i64, u32, vp], c_int),
+        "et_weighted_weight_grad": ([c_int, vp, i32, vp], c_int),
+        "et_weighted_sgd_workspace_size": ([vp, i32, vp], c_int),
+        "et_weighted_sgd": ([c_int, vp, i32, dbl, u32, vp, i64, vp], c_int),
         "et_adagrad_workspace_size": ([vp, i32, vp], c_int),
         "et_sparse_adagrad": ([c_int, vp, i32, dbl, dbl, u32, vp, i64, vp], c_int),
         "et_quantize_rows": ([vp, i64, i64, i32, i32, vp, i64, vp, vp], c_int),

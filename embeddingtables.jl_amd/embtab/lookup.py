@@ -23,6 +23,7 @@ from . import _lib
 from .quant import QuantizedEmbedding, is_quantized_list, quant_descs, quant_launch
 from .ragged import RaggedIndices, arithmetic_colptr
 from .tables import AbstractEmbeddingTable, ArgumentError, featuresize, example
+from .weighted import WeightedIndices, weighted_desc, weighted_launch
 
 
 class AbstractExecutionStrategy:
@@ -75,7 +76,7 @@ def _check_table(A):
 
 
 def _check_idx(I: torch.Tensor) -> torch.Tensor:
-    if isinstance(I, RaggedIndices):
+    if isinstance(I, (RaggedIndices, WeightedIndices)):
         if not I.is_cuda:
             raise ArgumentError("indices must be in device memory")
         return I
@@ -116,7 +117,7 @@ def _check_dst(dst: torch.Tensor, A, B: int):
 
 def _trailing_size(I: torch.Tensor) -> int:
     """src/lookup.jl:19: size(I, ndims(I)) — the batch (torch dim 0)."""
-    if isinstance(I, RaggedIndices):
+    if isinstance(I, (RaggedIndices, WeightedIndices)):
         return I.batch
     return int(I.shape[0])
 
@@ -148,6 +149,10 @@ def lookup_(dst: torch.Tensor, A: AbstractEmbeddingTable, I: torch.Tensor,
     L = _lib.load()
     D, R = A.size()
     flags = _lib.ET_FLAG_NONTEMPORAL if nontemporal else 0
+    if isinstance(I, WeightedIndices):  # weighted / mean bags: one table of the weighted entry
+        descs = (_lib.WeightedDesc * 1)(weighted_desc(A, I, 0))
+        weighted_launch(descs, 1, B, dst, _ld(dst), flags)
+        return dst
     if isinstance(A, QuantizedEmbedding):  # one et_quant_maplookup_prealloc launch
         quant_launch(quant_descs([A], [I], B, 0), 1, B, dst, _ld(dst), flags)
         return dst
@@ -241,11 +246,14 @@ def maplookup_(strategy: AbstractExecutionStrategy, dst, tables, I, nontemporal:
     return PreallocationPlan(strategy, dst, tables, Is, nontemporal, f16_fp32_acc)()
 
 
-def _fixed_descs(tables, Is, B: int, k: int, dtype):
-    """et_lookup_desc array of a list of fixed-pool (matrix or vector) indices."""
+def _fixed_descs(tables, Is, B: int, k: int, dtype, offs=None):
+    """et_lookup_desc array of a list of fixed-pool (matrix or vector) indices; `offs` gives
+    every table's first destination row (default: back to back from `k`)."""
     descs = (_lib.LookupDesc * len(tables))()
     off = k
     for t, (A, i) in enumerate(zip(tables, Is)):
+        if offs is not None:
+            off = offs[t]
         _check_table(A)
         _check_idx(i)
         if A.dtype != dtype:
@@ -263,7 +271,7 @@ def _fixed_descs(tables, Is, B: int, k: int, dtype):
     return descs
 
 
-def _ragged_descs(tables, Is, B: int, k: int, dtype):
+def _ragged_descs(tables, Is, B: int, k: int, dtype, offs=None):
     """et_ragged_desc array for a list in which some table's indices are RaggedIndices: a
     fixed-pool ``(B, P)`` matrix or a vector rides along as the ragged index it is, with the
     arithmetic colptr ``1 + P * (0:B)`` (its bags must then be back to back: ``ld == P``).
@@ -272,6 +280,8 @@ def _ragged_descs(tables, Is, B: int, k: int, dtype):
     keep = {}
     off = k
     for t, (A, i) in enumerate(zip(tables, Is)):
+        if offs is not None:
+            off = offs[t]
         _check_table(A)
         _check_idx(i)
         if A.dtype != dtype:
@@ -348,7 +358,45 @@ class PreallocationPlan:
         if k + sum(featuresize(t) for t in tables) > dst.shape[1]:
             raise ArgumentError("destination has too few rows for prependrows + sum(D)")
         dtype = tables[0].dtype  # the tables' element type; dst may be another (U)
+        # Weighted / mean tables go through one et_weighted_maplookup_prealloc call of their
+        # own, each with its own first row; the others take the usual path exactly as they
+        # would without them (two launches, so no existing result moves).
+        self._wn, offs = 0, None
+        wpos = [t for t, i in enumerate(Is) if isinstance(i, WeightedIndices)]
+        if wpos:
+            if dst.dtype != dtype:
+                raise NotImplementedError(
+                    "PreallocationStrategy(k, eltype=U) with weighted indices: the weighted "
+                    "launch writes the tables' element type")
+            offs, off = [], k
+            for A in tables:
+                offs.append(off)
+                off += featuresize(A)
+            for t in wpos:
+                _check_table(tables[t])
+                _check_idx(Is[t])
+                if tables[t].dtype != dtype:
+                    raise NotImplementedError(
+                        f"table {t} eltype {tables[t].dtype} != table 0 eltype {dtype}: one "
+                        "launch takes tables of one element type")
+                if _trailing_size(Is[t]) != B:
+                    raise ArgumentError(f"table {t}: batch {_trailing_size(Is[t])} != {B}")
+            self._wdescs = (_lib.WeightedDesc * len(wpos))(
+                *[weighted_desc(tables[t], Is[t], offs[t]) for t in wpos])
+            self._wn = len(wpos)
+            self._wkeep = (dst, [tables[t] for t in wpos], [Is[t] for t in wpos])
+            self._wflags = _lib.ET_FLAG_NONTEMPORAL if nontemporal else 0
+            rest = [t for t in range(len(tables)) if t not in set(wpos)]
+            tables, Is = [tables[t] for t in rest], [Is[t] for t in rest]
+            offs = [offs[t] for t in rest]
+            self._dst, self._ld, self._B = dst, _ld(dst), B
+            self._quant = False
+            self._n = 0
+            if not tables:
+                return
         self._quant = is_quantized_list(tables)  # all quantised, or none (a mix raises)
+        if self._quant and wpos:
+            raise ArgumentError("quantised tables beside weighted indices in one maplookup")
         if self._quant:  # fixed-pool and ragged indices alike: et_quant_maplookup_prealloc
             if f16_fp32_acc:
                 raise ArgumentError("f16_fp32_acc belongs to Float16 tables: a quantised lookup "
@@ -366,9 +414,9 @@ class PreallocationPlan:
                 "PreallocationStrategy(k, eltype=U) with ragged indices: the ragged launch "
                 "writes the tables' element type")
         if self._ragged:  # one fused et_ragged_maplookup_prealloc instead
-            descs, self._colptrs = _ragged_descs(tables, Is, B, k, dtype)
+            descs, self._colptrs = _ragged_descs(tables, Is, B, k, dtype, offs)
         else:
-            descs = _fixed_descs(tables, Is, B, k, dtype)
+            descs = _fixed_descs(tables, Is, B, k, dtype, offs)
         self._keep = (dst, tables, Is)  # the buffers the descriptors point into
         self._descs = descs
         self._n = len(tables)
@@ -385,6 +433,10 @@ class PreallocationPlan:
     def __call__(self):
         """Launch on the current stream; returns the destination."""
         dst = self._dst
+        if self._wn:  # the weighted / mean tables, then the others as ever
+            weighted_launch(self._wdescs, self._wn, self._B, dst, self._ld, self._wflags)
+            if self._n == 0:
+                return dst
         if self._quant:
             quant_launch(self._descs, self._n, self._B, dst, self._ld, self._flags)
             return dst

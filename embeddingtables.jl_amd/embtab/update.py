@@ -26,17 +26,32 @@ from .quant import refuse as refuse_quantized
 from .ragged import RaggedIndices
 from .tables import (AbstractEmbeddingTable, AbstractLookupType, ArgumentError, Dynamic,
                      featuresize, fused_update_path)
+from .weighted import (WeightedIndices, acc_dtype, as_ragged, mean_weights, weight_grad,
+                       weighted_update_desc)
 
 
 class SparseEmbeddingUpdate:
     """Lazy gradient of a lookup: ``delta`` (the output gradient, a ``(B, D)`` tensor,
     possibly a column block of a Preallocation gradient) and the forward ``indices``
-    (src/sparseupdate.jl:6-13).  Nothing is copied."""
+    (src/sparseupdate.jl:6-13).  Nothing is copied.
 
-    def __init__(self, lookup_type: AbstractLookupType, delta: torch.Tensor, indices):
+    ``weights`` (optional, beyond the reference): one weight per entry of the indices, of
+    the table's accumulator type — the gradient of a weighted or mean-pooled lookup, in which
+    entry ``k`` contributes ``weights[k] * delta[bag(k)]``."""
+
+    def __init__(self, lookup_type: AbstractLookupType, delta: torch.Tensor, indices,
+                 weights: torch.Tensor | None = None):
         self.lookup_type = lookup_type
         self.delta = delta
         self.indices = indices
+        self.weights = weights
+        self._ragged = None
+
+    def ragged(self) -> RaggedIndices:
+        """The indices as the ragged index the weighted kernels walk (built once)."""
+        if self._ragged is None:
+            self._ragged = as_ragged(self.indices)
+        return self._ragged
 
     def __repr__(self):
         I = self.indices
@@ -49,6 +64,20 @@ def uncompress(x: SparseEmbeddingUpdate, dstcols: int | None = None,
     """Densify a sparse gradient into a ``(dstcols, D)`` tensor (src/sparseupdate.jl:16-32).
     A test helper in the reference; done with device tensor ops here."""
     I = x.indices
+    if x.weights is not None:
+        # weighted: entry k adds weights[k] * delta[bag(k)]
+        R_ = x.ragged()
+        bag = R_.bag_ids()
+        nb = x.delta.shape[0] if maxindices is None else min(maxindices, x.delta.shape[0])
+        use = (bag > 0) & (bag <= nb)
+        cols, bag = R_.values[use] - 1, bag[use] - 1
+        if dstcols is None:
+            dstcols = int(cols.max().item()) + 1 if cols.numel() else 0
+        dst = torch.zeros((dstcols, x.delta.shape[1]), dtype=x.delta.dtype,
+                          device=x.delta.device)
+        w = x.weights.reshape(-1)[use].to(x.delta.dtype)
+        dst.index_add_(0, cols, x.delta[bag] * w[:, None])
+        return dst
     if isinstance(I, RaggedIndices):
         # every entry's gradient column is its bag (0: the capacity tail, no bag)
         bag = I.bag_ids()
@@ -85,6 +114,9 @@ def rrule(f, *args):
         y = lookup(A, I)
 
         def lookup_pullback(delta):
+            if isinstance(I, WeightedIndices):
+                g, dw = _weighted_pullback(A, delta, I)
+                return (NoTangent(), g, dw)
             return (NoTangent(), SparseEmbeddingUpdate(S, delta, I), NoTangent())
 
         return y, lookup_pullback
@@ -99,19 +131,55 @@ def rrule(f, *args):
             # prependrows + sum(D[<t]) .+ (1:D_t) of the gradient.
             def maplookup_pullback(delta):
                 off = strategy.prependrows
-                grads = []
+                grads, dws = [], []
                 for A, i in zip(tables, Is):
                     D = featuresize(A)
-                    grads.append(SparseEmbeddingUpdate(A.lookup_type, delta[:, off:off + D], i))
+                    g, dw = _pullback_one(A, delta[:, off:off + D], i)
+                    grads.append(g)
+                    dws.append(dw)
                     off += D
-                return (NoTangent(), NoTangent(), grads, NoTangent())
+                return (NoTangent(), NoTangent(), grads, _index_tangents(dws))
         else:
             def maplookup_pullback(deltas):
-                grads = [SparseEmbeddingUpdate(A.lookup_type, d, i)
-                         for A, d, i in zip(tables, deltas, Is)]
-                return (NoTangent(), NoTangent(), grads, NoTangent())
+                both = [_pullback_one(A, d, i) for A, d, i in zip(tables, deltas, Is)]
+                return (NoTangent(), NoTangent(), [g for g, _ in both],
+                        _index_tangents([dw for _, dw in both]))
         return y, maplookup_pullback
     raise NotImplementedError(f"no rrule for {f!r}")
+
+
+def _weighted_pullback(A, delta, I: WeightedIndices):
+    """(table gradient, tangent of the indices) of a weighted / mean lookup.  The table
+    gradient carries the weights (``1 / len(bag)`` per entry for mean mode, built on the
+    device without a synchronisation); ``dw`` is computed here, eagerly, from the table as it
+    is now — before any update can run."""
+    C = acc_dtype(A.dtype)
+    if I.mode == "mean":
+        w = mean_weights(I.ragged, C)
+    elif I.weights is not None:
+        w = I.weights.reshape(-1)
+    else:  # an unweighted sum: the plain gradient
+        return SparseEmbeddingUpdate(A.lookup_type, delta, I.indices), NoTangent()
+    g = SparseEmbeddingUpdate(A.lookup_type, delta, I.indices, w)
+    g._ragged = I.ragged
+    dw = NoTangent()
+    if I.weight_grad:
+        dw = weight_grad(A, delta, I.ragged).view(I.weights.shape)
+    return g, dw
+
+
+def _pullback_one(A, delta, i):
+    if isinstance(i, WeightedIndices):
+        return _weighted_pullback(A, delta, i)
+    return SparseEmbeddingUpdate(A.lookup_type, delta, i), NoTangent()
+
+
+def _index_tangents(dws):
+    """NoTangent() as ever unless some entry asked for its weight gradient: then a list, with
+    NoTangent() for the entries that have none."""
+    if all(isinstance(d, NoTangent) for d in dws):
+        return NoTangent()
+    return dws
 
 
 # --- optimiser -----------------------------------------------------------------------------
@@ -454,6 +522,39 @@ def _ragged_sgd(descs, eta: float, flags: int, device, dtype, key: str = "ragged
                                flags, ws.data_ptr(), ws.numel(), _lib.stream_handle(device)))
 
 
+def _weighted_sgd(descs, eta: float, flags: int, device, dtype, key: str = "weighted_sgd"):
+    """One et_weighted_sgd call over gradients that carry weights (always exact, caller's
+    stream only)."""
+    L = _lib.load()
+    n = len(descs)
+    arr = (_lib.WeightedUpdateDesc * n)(*descs)
+    nb = ctypes.c_int64(0)
+    _lib.check(L.et_weighted_sgd_workspace_size(ctypes.addressof(arr), n, ctypes.byref(nb)))
+    ws = _workspace(nb.value, device, key)
+    _lib.check(L.et_weighted_sgd(_lib.TORCH_TO_ET[dtype], ctypes.addressof(arr), n, float(eta),
+                                 flags, ws.data_ptr(), ws.numel(), _lib.stream_handle(device)))
+
+
+def _weighted_grad_desc(table, grad: "SparseEmbeddingUpdate", exact) -> _lib.WeightedUpdateDesc:
+    if exact is False:
+        raise ArgumentError("exact=False with a weighted gradient: et_weighted_sgd is always "
+                            "the exact serial sum")
+    if table.dtype not in _UPDATE_DTYPES:
+        raise NotImplementedError(f"update of a {table.dtype} table")
+    r = grad.ragged()
+    if not r.is_cuda:
+        raise ArgumentError("indices must be in device memory")
+    return weighted_update_desc(table, grad.delta, r, grad.weights.reshape(-1), None)
+
+
+def _defer_weighted(indexer, grad: "SparseEmbeddingUpdate", maxindex: int):
+    """Fill a caller's Indexer from the indices, as the other paths do: built on first use
+    from a copy taken now, in stream order."""
+    if isinstance(indexer, Indexer):
+        I = grad.indices
+        indexer._pending = (I.clone(), int(maxindex))
+
+
 def _sparse_sgd(descs, eta: float, flags: int, device, dtype=torch.float32, snaps=None):
     """One et_sparse_sgd call; `snaps` (one device pointer or None per descriptor) makes it
     et_sparse_sgd_snap, whose key pass copies those tables' index arrays."""
@@ -514,6 +615,13 @@ def update_(*args, nontemporal: bool | None = None, exact: bool | None = None,
     updated in one call per (path, eltype) group ahead of the others, which take the usual
     path; a ``telemetry_cb`` runs after the ragged tables' update is enqueued.
 
+    A gradient that carries ``weights`` (the pullback of a weighted or mean-pooled lookup,
+    ``WeightedIndices``) goes through et_weighted_sgd: entry ``k`` adds
+    ``weights[k] * delta[bag(k)]``, always the exact serial sum (``exact=False`` raises
+    ``ArgumentError``; a hot column is one serial chain on one wave).  In a multi-table call
+    such gradients are grouped into their own call per (path, eltype), ahead of the ragged
+    and the fixed-pool ones.  ``AdaGrad``, ``PhasedUpdate`` and the Indexer form refuse them.
+
     * ``update_(opt::AdaGrad, table, grad)`` and ``update_(opt::AdaGrad, tables, grads)`` —
       sparse AdaGrad (et_sparse_adagrad), fixed-pool and ragged gradients in the same call,
       one call per element type and at most ET_MAX_TABLES_PER_LAUNCH tables.  ``nontemporal``
@@ -567,6 +675,15 @@ def _update_single(opt: Descent, table, grad: SparseEmbeddingUpdate, nontemporal
     the update from it.  The device pipeline indexes on its own; a caller-supplied Indexer is
     filled as the reference's is, from a snapshot of the indices the update's key pass takes
     (et_sparse_sgd_snap), built into the reference layout on first use (Indexer._defer)."""
+    if grad.weights is not None:
+        # weighted gradient (a weighted or mean-pooled lookup): et_weighted_sgd
+        d = _weighted_grad_desc(table, grad, exact)
+        _defer_weighted(indexer, grad, table.size()[1])
+        if d.nnz == 0 or d.batch == 0:
+            return
+        _weighted_sgd([d], opt.eta, _sgd_flags(fused_update_path(table), nontemporal, False,
+                                               exact, f16_fp32_acc), table.device, table.dtype)
+        return
     if isinstance(grad.indices, RaggedIndices):
         # ragged gradient: always the exact serial sum, whatever `exact` says; no hot pass
         if isinstance(indexer, Indexer):
@@ -611,6 +728,32 @@ def _update_multi(opt: Descent, tables, grads, nontemporal: bool, exact: bool | 
         indexers = list(indexers)
         if len(indexers) != len(grads):
             raise ArgumentError("indexers and grads differ in length")
+    wtd = [i for i, g in enumerate(grads) if g.weights is not None]
+    if wtd:
+        # gradients that carry weights: their own et_weighted_sgd call per (path, eltype)
+        # group, ahead of the others, as the ragged ones below
+        wgroups: dict = {}
+        for i in wtd:
+            A, g = tables[i], grads[i]
+            d = _weighted_grad_desc(A, g, exact)
+            if indexers is not None:
+                _defer_weighted(indexers[i], g, A.size()[1])
+            if d.nnz == 0 or d.batch == 0:
+                continue
+            wgroups.setdefault((fused_update_path(A), A.dtype), []).append(d)
+        ncall = 0
+        for (fused, dtype), descs in wgroups.items():
+            for c in range(0, len(descs), _lib.ET_MAX_TABLES_PER_LAUNCH):
+                _weighted_sgd(descs[c:c + _lib.ET_MAX_TABLES_PER_LAUNCH], opt.eta,
+                              _sgd_flags(fused, nontemporal, not fused, exact, f16_fp32_acc),
+                              tables[0].device, dtype, f"weighted_sgd{ncall}")
+                ncall += 1
+        rest = [i for i in range(len(grads)) if i not in set(wtd)]
+        return _update_multi(opt, [tables[i] for i in rest], [grads[i] for i in rest],
+                             nontemporal, exact, f16_fp32_acc, num_splits, nthreads,
+                             scratchspaces, telemetry_cb,
+                             None if indexers is None else [indexers[i] for i in rest],
+                             hot_pass)
     rag = [i for i, g in enumerate(grads) if isinstance(g.indices, RaggedIndices)]
     if rag:
         # a mixed list is split: the ragged tables in one et_ragged_sgd call per (path,
@@ -722,6 +865,9 @@ def _update_adagrad(opt: AdaGrad, tables, grads, nontemporal: bool):
     tables; fixed-pool and ragged gradients stay in the same call, empty ones are skipped."""
     if len(tables) != len(grads):
         raise ArgumentError("tables and grads differ in length")
+    if any(g.weights is not None for g in grads):
+        raise ArgumentError("AdaGrad with a weighted gradient: weighted AdaGrad is not "
+                            "implemented (Descent only)")
     groups: dict = {}
     for A, g in zip(tables, grads):
         I = g.indices
@@ -752,6 +898,9 @@ def _update_adagrad(opt: AdaGrad, tables, grads, nontemporal: bool):
 
 def _update_from_indexer(table, grad: SparseEmbeddingUpdate, indexer: AbstractIndexer,
                          alpha: float, nontemporal: bool, f16_fp32_acc: bool = False):
+    if grad.weights is not None:
+        raise ArgumentError("update_ from an Indexer ignores weights: use update_(Descent, "
+                            "table, grad) for a weighted gradient")
     base = indexer.I if isinstance(indexer, IndexerView) else indexer
     if base.cumulative is None:
         raise ArgumentError("indexer is empty: call index_(indexer, grad.indices, maxindex)")
@@ -795,6 +944,9 @@ class PhasedUpdate:
         refuse_quantized(tables, "PhasedUpdate")
         if len(tables) != len(grads):
             raise ArgumentError("tables and grads differ in length")
+        if any(g.weights is not None for g in grads):
+            raise ArgumentError("PhasedUpdate with a weighted gradient: et_weighted_sgd has no "
+                                "phased form")
         if any(isinstance(g.indices, RaggedIndices) for g in grads):
             raise NotImplementedError("PhasedUpdate with a ragged gradient: et_ragged_sgd has "
                                       "no phased form")

@@ -788,6 +788,135 @@ function update!(opt::Flux.Descent, table::HipTable{S,T}, grad::RaggedEmbeddingU
 end
 
 #####
+##### Weighted and mean-pooled bags (no counterpart in the reference; include/embtab.h
+##### "Weighted and mean-pooled bags" states the arithmetic).  `weights` pairs entry k of the
+##### values with weights[k]; its element type is the accumulator type of the table (Float32,
+##### Float64 for Float64 tables).  `mode` is :sum or :mean (mean takes no weights).
+#####
+
+const ET_POOL_SUM = Int32(0)
+const ET_POOL_MEAN = Int32(1)
+acc_eltype(::Type{T}) where {T} = T === Float64 ? Float64 : Float32
+
+struct WeightedIndices{W}
+    indices::RaggedIndices
+    weights::W               # HipVector of the accumulator type, or nothing
+    mode::Symbol
+    function WeightedIndices(indices::RaggedIndices, weights = nothing; mode::Symbol = :sum)
+        mode in (:sum, :mean) || throw(ArgumentError("mode $mode: :sum or :mean"))
+        mode === :mean && weights !== nothing &&
+            throw(ArgumentError("mode = :mean takes no weights"))
+        weights === nothing || length(weights) == length(indices.values) ||
+            throw(ArgumentError("weights need one entry per entry of the values"))
+        return new{typeof(weights)}(indices, weights, mode)
+    end
+end
+# a dense P x B index matrix is the ragged index with this colptr, 1 + P*(0:B), over the
+# matrix's own memory
+arithmetic_colptr(P::Integer, B::Integer) = upload(collect(1:P:(P * B + 1)))
+batchsize(W::WeightedIndices) = batchsize(W.indices)
+
+struct WeightedDesc
+    table::Ptr{Cvoid}
+    ld_table::Int64
+    nrows::Int64
+    dim::Int32
+    mode::Int32
+    idx::Ptr{Int64}
+    nnz::Int64
+    colptr::Ptr{Int64}
+    dst_row_off::Int64
+    cols_per_page::Int64
+    weights::Ptr{Cvoid}
+end
+
+struct WeightedUpdateDesc
+    table::Ptr{Cvoid}
+    ld_table::Int64
+    nrows::Int64
+    dim::Int32
+    reserved::Int32
+    delta::Ptr{Cvoid}
+    ld_delta::Int64
+    idx::Ptr{Int64}
+    nnz::Int64
+    colptr::Ptr{Int64}
+    batch::Int64
+    cols_per_page::Int64
+    weights::Ptr{Cvoid}
+    dweights::Ptr{Cvoid}
+end
+
+_weights_ptr(::Type{T}, ::Nothing) where {T} = Ptr{Cvoid}(C_NULL)
+function _weights_ptr(::Type{T}, w) where {T}
+    eltype(w) === acc_eltype(T) ||
+        throw(ArgumentError("weights of $(eltype(w)) with a $T table: $(acc_eltype(T)) expected"))
+    return Ptr{Cvoid}(w.ptr)
+end
+
+function _weighted_desc(A::HipTable{S,T}, W::WeightedIndices, off) where {S,T}
+    tp, ldt, cpp = _device_table(A)
+    R = W.indices
+    return WeightedDesc(tp, ldt, size(A, 2), size(A, 1),
+                        W.mode === :mean ? ET_POOL_MEAN : ET_POOL_SUM, R.values.ptr,
+                        length(R.values), R.colptr.ptr, off, cpp, _weights_ptr(T, W.weights))
+end
+
+function lookup!(dst, A::HipTable{S,T}, W::WeightedIndices) where {S,T}
+    p, ld = _ptr_ld(dst)
+    descs = [_weighted_desc(A, W, 0)]
+    check(ccall((:et_weighted_maplookup_prealloc, libembtab), Cint,
+                (Cint, Ptr{WeightedDesc}, Int32, Int64, Ptr{Cvoid}, Int64, UInt32, Ptr{Cvoid}),
+                et_dtype(T), descs, length(descs), batchsize(W), p, ld, ET_FLAG_NONTEMPORAL,
+                stream()))
+    return dst
+end
+
+# The gradient of a weighted or mean-pooled lookup: entry k adds weights[k] * delta[:, bag(k)].
+struct WeightedEmbeddingUpdate{D,W}
+    delta::D
+    indices::RaggedIndices
+    weights::W
+end
+
+function _weighted_update_desc(table::HipTable{S,T}, delta, R::RaggedIndices, w, dw) where {S,T}
+    dp, dld = _ptr_ld(delta)
+    tp, ldt, cpp = _device_table(table)
+    return WeightedUpdateDesc(tp, ldt, size(table, 2), size(table, 1), 0, dp, dld, R.values.ptr,
+                              length(R.values), R.colptr.ptr, batchsize(R), cpp,
+                              _weights_ptr(T, w), _weights_ptr(T, dw))
+end
+
+# dw[k] = dot(delta[:, bag(k)], table[:, values[k]]), +0 where no bag covers k; reads the
+# table as it is now, so call it before the update
+function weight_grad(table::HipTable{S,T}, delta, R::RaggedIndices) where {S,T<:UpdateEltype}
+    dw = HipArray{acc_eltype(T)}(undef, length(R.values))
+    descs = [_weighted_update_desc(table, delta, R, nothing, dw)]
+    check(ccall((:et_weighted_weight_grad, libembtab), Cint,
+                (Cint, Ptr{WeightedUpdateDesc}, Int32, Ptr{Cvoid}),
+                et_dtype(T), descs, length(descs), stream()))
+    return dw
+end
+
+function update!(opt::Flux.Descent, table::HipTable{S,T}, grad::WeightedEmbeddingUpdate,
+                 ::Val{Nontemporal} = Val(true)) where {S,T<:UpdateEltype,Nontemporal}
+    isempty(grad.indices) && return nothing
+    flags = (Nontemporal ? ET_FLAG_NONTEMPORAL : UInt32(0)) |
+            (_fused(table) ? UInt32(0) : ET_FLAG_SGD_UNFUSED)
+    descs = [_weighted_update_desc(table, grad.delta, grad.indices, grad.weights, nothing)]
+    nb = Ref{Int64}(0)
+    check(ccall((:et_weighted_sgd_workspace_size, libembtab), Cint,
+                (Ptr{WeightedUpdateDesc}, Int32, Ref{Int64}), descs, length(descs), nb))
+    ws = _workspace(nb[], -3)
+    check(ccall((:et_weighted_sgd, libembtab), Cint,
+                (Cint, Ptr{WeightedUpdateDesc}, Int32, Float64, UInt32, Ptr{Cvoid}, Int64,
+                 Ptr{Cvoid}),
+                et_dtype(T), descs, length(descs), Float64(opt.eta), flags, ws.ptr, length(ws),
+                stream()))
+    return nothing
+end
+
+#####
 ##### Sparse AdaGrad (no counterpart in the reference, whose only optimiser is Descent;
 ##### include/embtab.h states the arithmetic, parity with Flux.ADAGrad is unpinned).  The
 ##### state lives in the optimiser, one device array per table object: dim x nrows
@@ -996,6 +1125,7 @@ end
 
 export QuantizedEmbedding, HipEmbedding, HipSplitEmbedding, HipArray, HipVector, HipMatrix, EmbtabError,
     DeviceColumns, HipIndexer, ShardedPreallocation, shard_plan, comm_id, comm_init,
-    comm_destroy, comm_loopback, RaggedIndices, RaggedEmbeddingUpdate, bag_ids
+    comm_destroy, comm_loopback, RaggedIndices, RaggedEmbeddingUpdate, bag_ids,
+    WeightedIndices, WeightedEmbeddingUpdate, weight_grad, arithmetic_colptr
 
 end # module

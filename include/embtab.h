@@ -367,6 +367,118 @@ int et_ragged_sgd(int dtype, const et_ragged_update_desc* descs, int32_t ntables
                   uint32_t flags, void* workspace, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Weighted and mean-pooled bags (EmbeddingBag's per_sample_weights and mode="mean").  The
+ * reference has neither: the definitions here are the contract.
+ *
+ * C is the accumulator type: Float32 for ET_F32 / ET_F16 / ET_BF16 tables, Float64 for ET_F64.
+ * Weights and weight gradients are ALWAYS of type C, whatever the table type.  Integer tables
+ * return ET_ERR_UNSUPPORTED.  Every operation below is rounded once in C and nothing is fused
+ * (the library is built with -ffp-contract=off); T(.) is one RNE rounding for 16-bit tables.
+ *
+ * Bags are the ragged form above: idx, colptr, the capacity nnz, the same clamping, each
+ * clamped bound counted.  `weights` has the capacity of idx and entry k of idx pairs with
+ * weights[k].  No kernel reads weights outside [0, nnz), or at an entry that no bag covers.
+ * A fixed-pool P x B index is the ragged index with colptr = 1 + P*(0:B).
+ *
+ * Forward, ET_POOL_SUM, for a bag [lo, hi):
+ *   an empty bag writes +0;
+ *   acc = C(w_lo) * C(x_lo);  for k = lo+1 .. hi-1:  t = C(w_k) * C(x_k);  acc = acc + t
+ *   out = T(acc)
+ *   An index outside 1..nrows is counted and takes x = +0; it is still multiplied, so the
+ *   sign of that zero follows the weight.  weights == NULL means no products: the sum starts
+ *   from a COPY of the first row, and the result equals et_ragged_maplookup_prealloc (with
+ *   ET_FLAG_F16_FP32_ACC for ET_F16) bit for bit.  So does the result with every weight 1.0,
+ *   and a one-entry bag of weight 1.0 on a row of -0.0 gives -0.0.
+ * Forward, ET_POOL_MEAN: weights must be NULL (ET_ERR_UNSUPPORTED otherwise); acc is the
+ *   unweighted sum and out = T(acc / C(hi - lo)), one correctly rounded division; entries
+ *   out of range count in the length; an empty bag writes +0.
+ * Weight gradient: for every entry k covered by a bag j,
+ *   dw[k] = sum_f C(delta[f, j]) * C(x_k[f]), formed in C; the order of the sum is the
+ *   kernel's choice but the same from run to run; an index out of range gives +0; every
+ *   entry of dw[0, nnz) that no bag covers is written +0 (a stream-ordered memset).  The
+ *   table is read as it is when the call runs: call it before the update.
+ * Weighted sparse SGD: et_ragged_sgd with a weight per entry.  For every distinct column,
+ *   acc = +0; for its participating entries in increasing k:
+ *   t = C(w_k) * C(delta[:, bag(k)]);  acc = acc + t;  then the update of et_sparse_sgd
+ *   (fused, ET_FLAG_SGD_UNFUSED, ET_FLAG_SGD_F64_ALPHA).  Always exact, never split: one
+ *   serial chain per column (a hot column costs what it costs et_ragged_sgd).  ET_F16 sums in
+ *   Float32 (ET_FLAG_F16_FP32_ACC is implied and accepted).  A column with no participating
+ *   entry is not written.  For ET_F32 / ET_F64 the result equals a vector-index et_sparse_sgd
+ *   of the expanded gradient E[:, k] = fl_C(w_k * delta[:, bag(k)]) bit for bit.
+ * Mean mode has no backward entry of its own: its pullback is the weighted update with
+ * w_k = 1 / len(bag(k)).
+ * ------------------------------------------------------------------------------- */
+#define ET_POOL_SUM 0
+#define ET_POOL_MEAN 1
+
+/* One table of a weighted / mean lookup: et_ragged_desc with a mode and the weights. */
+typedef struct et_weighted_desc {
+    const void* table;     /* as in et_lookup_desc */
+    int64_t ld_table;
+    int64_t nrows;
+    int32_t dim;
+    int32_t mode;          /* ET_POOL_SUM or ET_POOL_MEAN */
+    const int64_t* idx;    /* device, the bags' indices back to back, 1-based Int64 */
+    int64_t nnz;           /* capacity of idx and of weights */
+    const int64_t* colptr; /* device, batch + 1 entries, 1-based, non-decreasing */
+    int64_t dst_row_off;   /* as in et_lookup_desc */
+    int64_t cols_per_page; /* as in et_lookup_desc */
+    const void* weights;   /* device, nnz entries of type C, or NULL (unweighted) */
+} et_weighted_desc;
+
+/* Fused weighted / mean lookup + concat (semantics above) into
+ * dst[desc[t].dst_row_off + (0:dim_t-1), j].  Weighted, unweighted and mean tables may share
+ * one call; ntables <= ET_MAX_TABLES_PER_LAUNCH; batch == 0 is a no-op.  Flags:
+ * ET_FLAG_NONTEMPORAL only (any other flag: ET_ERR_UNSUPPORTED).  Every argument error (NULLs,
+ * negative sizes, ld_table < dim, rows outside ld_dst, a mode that is neither, too many
+ * tables; weights with ET_POOL_MEAN and integer dtypes: ET_ERR_UNSUPPORTED) is reported before
+ * any device work.  Stream-ordered on the caller's stream only, allocates nothing, never
+ * synchronises: capturable. */
+int et_weighted_maplookup_prealloc(int dtype, const et_weighted_desc* descs, int32_t ntables,
+                                   int64_t batch, void* dst, int64_t ld_dst, uint32_t flags,
+                                   void* stream);
+
+/* One table of a weighted update or weight gradient: et_ragged_update_desc, the weights and
+ * the weight gradient. */
+typedef struct et_weighted_update_desc {
+    void* table;           /* device pointer (updated in place by et_weighted_sgd) */
+    int64_t ld_table;
+    int64_t nrows;
+    int32_t dim;
+    int32_t reserved;      /* 0 */
+    const void* delta;     /* dim x batch gradient, column j at delta + j*ld_delta */
+    int64_t ld_delta;
+    const int64_t* idx;    /* the values of the forward lookup */
+    int64_t nnz;           /* capacity of idx, weights and dweights */
+    const int64_t* colptr; /* batch + 1 entries */
+    int64_t batch;
+    int64_t cols_per_page; /* as in et_lookup_desc */
+    const void* weights;   /* type C, nnz entries: read by et_weighted_sgd only */
+    void* dweights;        /* type C, nnz entries: written by et_weighted_weight_grad only */
+} et_weighted_update_desc;
+
+/* dweights[0, nnz) of every table (semantics above): reads table, delta, idx and colptr,
+ * writes dweights, ignores weights.  ET_ERR_ARG before any device work: NULLs (dweights
+ * included), negative sizes, a leading dimension below dim, too many tables.  Stream-ordered
+ * on the caller's stream only (a memset, then the kernels), no allocation, no
+ * synchronisation: capturable. */
+int et_weighted_weight_grad(int dtype, const et_weighted_update_desc* descs, int32_t ntables,
+                            void* stream);
+
+/* Bytes of device workspace et_weighted_sgd needs: et_ragged_sgd_workspace_size of the same
+ * sizes. */
+int et_weighted_sgd_workspace_size(const et_weighted_update_desc* descs, int32_t ntables,
+                                   int64_t* bytes);
+
+/* Weighted sparse SGD (semantics above); ignores dweights.  weights == NULL of a table with
+ * work is ET_ERR_ARG; ET_FLAG_SGD_INDEX_ONLY, ET_FLAG_SGD_APPLY_ONLY and ET_FLAG_SGD_HOT_PASS
+ * return ET_ERR_UNSUPPORTED; ET_FLAG_EXACT_UPDATE, ET_FLAG_EXACT_IF_FAST and
+ * ET_FLAG_F16_FP32_ACC are accepted and change nothing.  Stream-ordered on the caller's stream
+ * only, no host synchronisation: capturable.  The sum of nnz must be below 2^31 - 1. */
+int et_weighted_sgd(int dtype, const et_weighted_update_desc* descs, int32_t ntables, double eta,
+                    uint32_t flags, void* workspace, int64_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Sparse AdaGrad, element-wise (Flux's ADAGrad) and row-wise, over fixed-pool and ragged
  * gradients.  The reference has no optimiser but Descent: this arithmetic is defined here,
  * and its parity with Flux is unpinned (as Float16 parity is).
