@@ -2232,7 +2232,12 @@ __device__ __forceinline__ void sgd_chain_item(const UpdatePack& pack, int ntabl
                 case 8: acc = chain_walk_asm<8>(e, c.ngr, rs, 4u * fc, 4u * ld, 0.0f); break;
                 default: acc = chain_walk_asm<16>(e, c.ngr, rs, 4u * fc, 4u * ld, 0.0f); break;
             }
-            done = true;
+            // A masked slot of those loops is fma(0, x, acc): acc for finite x, NaN once the
+            // sum has reached +-Inf (0 * Inf), where the reference's adds keep the Inf.  So a
+            // NaN in any lane sends the slice through the real adds again; a sum that is
+            // truly NaN comes out NaN again.  One compare and a not-taken branch otherwise.
+            done = __builtin_amdgcn_ballot_w64(acc != acc) == 0ull;
+            if (!done) acc = C(0);
         }
     }
     if (!done)

@@ -29,6 +29,19 @@
  * (`@inbounds`, src/lookup.jl).  Here they never fault the GPU: a bad index
  * contributes a zero row (lookup) or is skipped (update), and is counted in a
  * device-side error word readable with `et_check_errors`.
+ *
+ * Special values.  Every sum, product and conversion below is the IEEE-754 operation of
+ * its type in round-to-nearest-even, with nothing flushed: subnormal inputs, sums and
+ * results are kept.  Signed zeros and +-Inf are bit-identical to the reference's CPU
+ * algorithms (a pooled sum starts with a copy of its first row, so a bag of -0 rows is
+ * -0; an empty bag and an update's column sum start from +0), and Inf stays Inf where the
+ * reference's adds keep it: Inf + x is never turned into NaN.  NaN is guaranteed by
+ * position, not by sign or payload (a generated NaN differs between platforms), except in
+ * pure copies: a vector-index gather, and a one-entry bag of a type that is its own
+ * accumulator, return the stored bits.  The zero row an out-of-range index contributes is
+ * a select, never a product: it is +0 whatever the table holds, NaN and Inf included.
+ * Where a definition multiplies (weights, row-wise scales), 0 * Inf and 0 * NaN are NaN
+ * as IEEE-754 has them.  Integer sums wrap.
  */
 #ifndef EMBTAB_H
 #define EMBTAB_H
