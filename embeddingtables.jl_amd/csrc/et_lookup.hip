@@ -486,6 +486,120 @@ __device__ __forceinline__ void run_bags_s(const et_lookup_desc& d, int64_t batc
     }
 }
 
+// ---------------------------------------------------------------------------
+// Bag loop of a COLUMN QUARTER of 512-byte rows (striped_body, a quartered entry): a group of 8
+// lanes holds 128 bytes of a row, a wave 8 bags, a workgroup round 32.  `d` is the table's
+// descriptor shifted to the quarter (table and dst_row_off).  It is the per-lane loop (run_bags at
+// a quarter of the row) with the addressing cut down for what a quartered table guarantees: its
+// bytes are below 2^31 (LookupTuning::quarter_max_bytes), so the lane that holds an index turns it
+// into a 32-bit byte offset once, a row costs one ds_bpermute of that offset plus one add of the
+// lane's 16-byte column, and the load takes the table base from scalar registers; the range check
+// is made once per index chunk for the whole wave, and only a chunk that holds an out-of-range
+// index pays the per-row zero selects (~0u marks it: no offset reaches 2^31).  The summation order
+// is the per-lane loop's (pool order from the first row): bit-identical.  count_bad = false: an
+// out-of-range index adds its zero row but is not counted (quarters 1-3: quarter 0 counted it).
+template <typename T, typename A, int UU>
+__device__ __forceinline__ void load_add_q(const char* __restrict__ tb, uint32_t myoff, int gaddr,
+                                           uint32_t lane_off, int i0, bool first_batch,
+                                           bool anybad, A (&acc)[16 / sizeof(T)], int& bad) {
+    constexpr int N = 16 / (int)sizeof(T);
+    uint32_t off[UU];
+#pragma unroll
+    for (int u = 0; u < UU; ++u)
+        off[u] = (uint32_t)__builtin_amdgcn_ds_bpermute(gaddr + 4 * (i0 + u), (int)myoff);
+    u32x4 buf[UU];
+    if (__builtin_expect(anybad, 0)) {
+#pragma unroll
+        for (int u = 0; u < UU; ++u) {
+            const bool ok = off[u] != ~0u;
+            bad += ok ? 0 : 1;
+            const u32x4 v = *reinterpret_cast<const u32x4*>(tb + ((ok ? off[u] : 0u) + lane_off));
+            buf[u] = ok ? v : u32x4{0u, 0u, 0u, 0u};
+        }
+    } else {
+#pragma unroll
+        for (int u = 0; u < UU; ++u)
+            buf[u] = *reinterpret_cast<const u32x4*>(tb + (off[u] + lane_off));
+    }
+#pragma unroll
+    for (int u = 0; u < UU; ++u) {
+        T x[N];
+        unpack16<T, N>(buf[u], x);
+#pragma unroll
+        for (int k = 0; k < N; ++k) {
+            if (u == 0)
+                acc[k] = first_batch ? A(x[k]) : A(acc[k] + A(x[k]));
+            else
+                acc[k] = A(acc[k] + A(x[k]));
+        }
+    }
+}
+
+template <typename T, typename A, int U, bool NT>
+__device__ __forceinline__ void run_bags_q(const et_lookup_desc& d, int64_t batch,
+                                           T* __restrict__ dst, int64_t ld_dst, int64_t chunk,
+                                           int rounds, bool count_bad) {
+    constexpr int N = 16 / (int)sizeof(T), LPR = 8, GPW = 8;
+    static_assert(U == 2 || U == 4 || U == 8, "rows in flight of the quarter loop");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane / LPR, sub = lane % LPR;
+    const int gaddr = (g * LPR) << 2;  // ds_bpermute address of the group's first lane
+    const uint32_t lane_off = (uint32_t)sub * 16u;
+    const char* tb = reinterpret_cast<const char*>(d.table);
+    const uint32_t ldb = (uint32_t)(d.ld_table * (int64_t)sizeof(T)), nr = (uint32_t)d.nrows;
+    const int pool = d.pool;
+    const int cnt0 = pool < LPR ? pool : LPR;
+    const int64_t per_round = 4 * GPW;
+    int64_t bag = chunk * per_round * rounds + wave * GPW + g;
+    long long my_next =
+        load_idx_chunk<LPR>(d.idx + (bag < batch ? bag : batch - 1) * d.ld_idx, cnt0, sub);
+    for (int r = 0; r < rounds; ++r) {
+        if (bag >= batch) break;
+        long long my = my_next;
+        const int64_t nbag = bag + per_round;
+        if (r + 1 < rounds)
+            my_next = load_idx_chunk<LPR>(
+                d.idx + (nbag < batch ? nbag : batch - 1) * d.ld_idx, cnt0, sub);
+        const int64_t* ip = d.idx + bag * d.ld_idx;
+        A acc[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) acc[k] = A(0);
+        int bad = 0;
+        for (int c0 = 0; c0 < pool; c0 += LPR) {
+            const int cnt = pool - c0 < LPR ? pool - c0 : LPR;
+            if (c0 != 0) my = load_idx_chunk<LPR>(ip + c0, cnt, sub);
+            const uint32_t row = idx_row32(my, nr);
+            const uint32_t myoff = row == ~0u ? ~0u : row * ldb;
+            const bool anybad = __any(row == ~0u) != 0;
+            int i0 = 0;
+#define ET_LOAD_ADD_Q(UU) \
+    load_add_q<T, A, UU>(tb, myoff, gaddr, lane_off, i0, c0 + i0 == 0, anybad, acc, bad)
+            for (; i0 + U <= cnt; i0 += U) ET_LOAD_ADD_Q(U);
+            if constexpr (U > 4) {
+                if (cnt - i0 >= 4) {
+                    ET_LOAD_ADD_Q(4);
+                    i0 += 4;
+                }
+            }
+            if constexpr (U > 2) {
+                if (cnt - i0 >= 2) {
+                    ET_LOAD_ADD_Q(2);
+                    i0 += 2;
+                }
+            }
+            if (cnt - i0 >= 1) ET_LOAD_ADD_Q(1);
+#undef ET_LOAD_ADD_Q
+        }
+        if (bad && sub == 0 && count_bad) note_oob(bad);
+        T y[N];
+#pragma unroll
+        for (int k = 0; k < N; ++k) y[k] = T(acc[k]);
+        store16<NT>(reinterpret_cast<u32x4*>(dst + bag * ld_dst + d.dst_row_off) + sub,
+                    pack16<T, N>(y));
+        bag = nbag;
+    }
+}
+
 // Pooled-sum kernel, vector path: grid = ntables * nchunks workgroups of 256.
 // SG: the scalar-addressed loop (512-byte rows, contiguous tables, no masking).
 template <typename T, typename A, int D, int U, bool NT, bool PG = false, bool MK = false,
@@ -516,9 +630,21 @@ static_assert(kXcds == et_order::kXcds && ET_MAX_TABLES_PER_LAUNCH == et_order::
 
 // 32-bit entries (table | stripe << 8) so the map is read with scalar loads (gfx950
 // has no scalar byte loads).
+//
+// Column quarters (DESIGN §4 "Column quarters").  A table too big for one L2 but whose quarter
+// fits (LookupTuning::quarter_min_bytes < bytes <= quarter_max_bytes, 512-byte rows) is cut by
+// columns instead: XCD x sums the 128-byte line x % 4 of every row for the bags of batch half
+// x / 4, so its L2 holds a quarter of the table and serves it like a light one.  Rows in flight
+// per group of the quarter loop (run_bags_q): 8 bags x kQuarterU rows x 128 B per wave, sized for
+// L2 hits (8 rows cost 74 VGPRs, two of the eight waves per SIMD, and measured no faster).
+#ifndef ET_QUARTER_U
+#define ET_QUARTER_U 4
+#endif
+constexpr int kQuarterU = ET_QUARTER_U;
 constexpr int kMaxStripeEntries = et_order::kMaxEntries;  // per XCD
 struct StripeMap {
-    // entry[x][k]: table (bits 0-7), stripe (8-15); every XCD has one entry per table
+    // entry[x][k]: table (bits 0-7), stripe (8-15); a quartered entry: batch half (8-15), column
+    // quarter (16-17), flag (bit 18) (et_lookup_order.h); every XCD has one entry per table
     uint32_t entry[kXcds][kMaxStripeEntries];
     int nent;
     uint32_t ntload_mask;  // bit t: non-temporal row loads for table t
@@ -543,6 +669,24 @@ __device__ __forceinline__ void striped_body(const LookupPack& pack, const Strip
     const int64_t j = slot / ntables;
     const uint32_t e = sm.entry[x][k];
     const int t = (int)(e & 0xff);
+    if constexpr (SG) {
+        // a quartered entry (et_lookup_order.h): one 128-byte column quarter of every row, for
+        // four times the bags, through the quarter loop (run_bags_q)
+        if (et_order::entry_quartered(e)) {
+            constexpr int DQ = D / 4;
+            static_assert(4 * VecGeom<T, DQ>::GPW == et_order::kQuarterBagsPerRound, "");
+            const et_order::ItemBags ib =
+                et_order::item_bags(e, j, stripe_chunks, nchunks, rounds, batch);
+            if (ib.count == 0) return;
+            const int q = (int)et_order::entry_quarter(e);
+            et_lookup_desc dq = pack.d[t];
+            dq.table = reinterpret_cast<const T*>(dq.table) + q * DQ;
+            dq.dst_row_off += q * DQ;
+            if ((sm.prio_mask >> t) & 1u) __builtin_amdgcn_s_setprio(2);
+            run_bags_q<T, A, kQuarterU, NT>(dq, batch, dst, ld_dst, ib.chunk, rounds, q == 0);
+            return;
+        }
+    }
     const int64_t chunk = (int64_t)((e >> 8) & 0xff) * stripe_chunks + j;
     if (j >= stripe_chunks || chunk >= nchunks) return;
     if ((sm.prio_mask >> t) & 1u) __builtin_amdgcn_s_setprio(2);
@@ -629,9 +773,11 @@ __global__ __launch_bounds__(256) void k_pooled_vec_striped(LookupPack pack, Str
 // stream could share one).  Which workgroup sums which bags never changes a result:
 // bit-identical to the static schedule.
 //
-// CU affinity (two class queues per XCD).  An XCD's entries are [0, nheavy): the FABRIC class
-// (tables above light_bytes, whose rows cross the fabric wherever they are read) and
-// [nheavy, nent): the CACHE class (light tables served by this XCD's L2).  With a preference
+// CU affinity (two class queues per XCD).  An XCD's entries (32 bits each: table in bits 0-7,
+// stripe in 8-15; a quartered entry carries the batch half in 8-15, the column quarter in 16-17
+// and a flag in bit 18) are [0, nheavy): the FABRIC class (tables above light_bytes, whose rows
+// cross the fabric wherever they are read) and [nheavy, nent): the CACHE class (light tables, and
+// the quartered ones when LookupTuning::quarter_cache, served by this XCD's L2).  With a preference
 // policy (sm.affinity != 0) every XCD has one head per class and a workgroup claims in this
 // order, x being the XCD it runs on:
 //   cache-preferring:   cache(x), fabric(x), fabric(other XCDs), cache(other XCDs)
@@ -994,6 +1140,16 @@ struct LookupTuning {
     // cache-class footprint above which an XCD runs its non-temporal phase first.  The sweep's
     // choice (profiles/r08/l2_order/sweep.txt): both classes table-major
     et_order::Policy order = {1, 3, 1 << 20};
+    // Column quarters (striped_body): contiguous tables of 512-byte rows above quarter_min_bytes
+    // and up to quarter_max_bytes (a quarter is then at most one L2) are cut by columns over the
+    // XCDs; quarter_max_bytes 0 = none.  quarter_cache: their entries join the cache class.
+    // ET_QUARTER_MIN, ET_QUARTER_MAX, ET_QUARTER_CLASS=fabric|cache
+    int64_t quarter_min_bytes = 4 << 20;
+    int64_t quarter_max_bytes = 16 << 20;
+    int quarter_cache = 1;
+    // fab_share of a launch whose cache class holds quartered tables: the class is that much
+    // larger (profiles/quarter/sweep.txt: 7 against 8, -0.023 ms); ET_FAB_SHARE sets both
+    int quarter_fab_share = 7;
 };
 
 inline const LookupTuning& tuning() {
@@ -1016,6 +1172,10 @@ inline const LookupTuning& tuning() {
         v.order.cache_major = (int)ET_KNOB("ET_ORDER_CACHE", v.order.cache_major);
         v.order.fab = (int)ET_KNOB("ET_ORDER_FAB", v.order.fab);
         v.order.phase_bytes = ET_KNOB("ET_PHASE_BYTES", v.order.phase_bytes);
+        v.quarter_min_bytes = ET_KNOB("ET_QUARTER_MIN", v.quarter_min_bytes);
+        v.quarter_max_bytes = ET_KNOB("ET_QUARTER_MAX", v.quarter_max_bytes);
+        if (const char* e = getenv("ET_QUARTER_CLASS")) v.quarter_cache = strcmp(e, "cache") == 0;
+        v.quarter_fab_share = (int)ET_KNOB("ET_FAB_SHARE", v.quarter_fab_share);
 #endif
         return v;
     }();
@@ -1026,30 +1186,43 @@ int max_rounds() { return tuning().max_rounds; }
 
 // Stripe assignment (et_order::place_stripes) and, for the class queues, the order in which
 // each class lists its entries (et_order::order_xcd).
-inline void build_stripe_map(const LookupPack& pack, int n, int es, bool queued, StripeMap& sm) {
+// sg: the launch takes the scalar-addressed 512-byte loop, so tables may be quartered.
+inline void build_stripe_map(const LookupPack& pack, int n, int es, bool queued, bool sg,
+                             StripeMap& sm) {
     const LookupTuning& tu = tuning();
-    int64_t bytes[ET_MAX_TABLES_PER_LAUNCH];
+    // foot: what one XCD's L2 holds of the table (a quarter of a quartered one): the class order
+    // sorts by it
+    int64_t bytes[ET_MAX_TABLES_PER_LAUNCH], foot[ET_MAX_TABLES_PER_LAUNCH];
+    uint32_t quarter_mask = 0;
     sm.ntload_mask = 0;
     sm.prio_mask = 0;
     for (int t = 0; t < n; ++t) {
         bytes[t] = pack.d[t].nrows * pack.d[t].ld_table * es;
+        foot[t] = bytes[t];
+        if (sg && pack.d[t].ld_table == pack.d[t].dim && bytes[t] > tu.quarter_min_bytes &&
+            bytes[t] <= tu.quarter_max_bytes && bytes[t] < (1ll << 31)) {  // run_bags_q: 32-bit offsets
+            quarter_mask |= 1u << t;
+            foot[t] = bytes[t] / 4;
+        }
         if (bytes[t] > tu.light_bytes) {
             if (tu.heavy_prio) sm.prio_mask |= 1u << t;
             if (tu.ntload && bytes[t] > tu.ntload_bytes) sm.ntload_mask |= 1u << t;
         }
     }
-    sm.nent = et_order::place_stripes(bytes, n, tu.light_bytes, sm.entry, &sm.nheavy);
+    sm.nent = et_order::place_stripes(bytes, n, tu.light_bytes, quarter_mask, tu.quarter_cache != 0,
+                                      sm.entry, &sm.nheavy);
     // a class preference needs both classes and a share to prefer by: otherwise none, the
     // one-queue schedule
     sm.affinity = sm.nheavy > 0 && sm.nheavy < sm.nent ? tu.affinity : 0;
-    sm.fab_share = tu.fab_share < 0 ? 0 : tu.fab_share > 16 ? 16 : tu.fab_share;
+    const int share = quarter_mask != 0 && tu.quarter_cache ? tu.quarter_fab_share : tu.fab_share;
+    sm.fab_share = share < 0 ? 0 : share > 16 ? 16 : share;
     if (sm.fab_share == 0) sm.affinity = 0;
     // the class queues' item order (only they have one: the one-queue schedule and the static
     // kernel keep the static order, so for them the entries stay as placed)
     memset(sm.order, 0, sizeof(sm.order));
     if (queued && sm.affinity != 0)
         for (int x = 0; x < kXcds; ++x)
-            et_order::order_xcd(sm.entry[x], x, sm.nent, sm.nheavy, bytes, sm.ntload_mask, tu.order,
+            et_order::order_xcd(sm.entry[x], x, sm.nent, sm.nheavy, foot, sm.ntload_mask, tu.order,
                                 sm.order);
 }
 
@@ -1073,7 +1246,7 @@ int launch_pooled_vec(const LookupPack& pack, int n, int64_t batch, void* dst, i
     int64_t stripe_chunks = 0, grid = nchunks * n;
     const bool queued = striped && pack.queue && tuning().queued;
     if (striped) {
-        build_stripe_map(pack, n, (int)sizeof(T), queued, sm);
+        build_stripe_map(pack, n, (int)sizeof(T), queued, sg, sm);
         stripe_chunks = (nchunks + kXcds - 1) / kXcds;
         grid = (int64_t)kXcds * sm.nent * stripe_chunks;
     }

@@ -2,7 +2,8 @@
 // pure index arithmetic, plain C++ with no HIP types, so a host program can include it
 // (tests/lookup_order_host.cpp) and the kernel and its test share one definition.
 //
-// An XCD owns `ntables` entries (one stripe each): [0, nheavy) the FABRIC class, [nheavy,
+// An XCD owns `ntables` entries (one stripe, or one column quarter of half the batch, each;
+// "entries" below): [0, nheavy) the FABRIC class, [nheavy,
 // ntables) the CACHE class.  Every entry has `sc` chunks; the item (chunk j of entry k) is slot
 // j * ntables + k of that XCD (striped_body's numbering, which never changes).  A class queue
 // hands out class slots h = 0, 1, 2 ...; the maps below say which item class slot h is.  A class's
@@ -59,23 +60,67 @@ ET_ORDER_FN uint32_t class_slot(const ClassOrder& o, uint32_t x, uint32_t c, uin
                       (o.major[x] >> 1) & 1u);
 }
 
-// ---- host side.  An entry is table | stripe << 8.
+// ---- entries.  A whole-row entry is table | stripe << 8: the XCD sums whole rows for the bags of
+// that stripe (an eighth of the table's chunks).  A QUARTERED entry is table | half << 8 |
+// quarter << 16 | kQuarterFlag: the XCD sums only column quarter `quarter` (one 128-byte line of
+// a 512-byte row) for the bags of batch half `half`, so of that table its L2 only ever holds
+// every fourth line.  A pooled sum is independent per column: the result does not change.
+
+constexpr uint32_t kQuarterFlag = 1u << 18;
+
+ET_ORDER_FN uint32_t entry_table(uint32_t e) { return e & 0xffu; }
+ET_ORDER_FN uint32_t entry_stripe(uint32_t e) { return (e >> 8) & 0xffu; }  // or the half
+ET_ORDER_FN uint32_t entry_quarter(uint32_t e) { return (e >> 16) & 3u; }
+ET_ORDER_FN bool entry_quartered(uint32_t e) { return (e & kQuarterFlag) != 0; }
+
+// Bags per workgroup round: the scalar-addressed whole-row loop holds two bags per wave; the
+// per-lane loop at a quarter of the row holds eight (a group is 8 lanes, not 32).
+constexpr int kRowBagsPerRound = 8, kQuarterBagsPerRound = 32;
+
+// Item (entry e, chunk j < sc) of a launch of `nchunks` whole-row chunks of kRowBagsPerRound *
+// rounds bags: its chunk number, and the bags [first, first + count) it sums (count 0: an empty
+// slot).  A quartered item's chunk is four times as many bags (the same bytes), and the two
+// halves' 2 * sc chunks reach the batch because 8 * sc >= nchunks.
+struct ItemBags {
+    int64_t chunk, first, count;
+};
+ET_ORDER_FN ItemBags item_bags(uint32_t e, int64_t j, int64_t sc, int64_t nchunks, int64_t rounds,
+                               int64_t batch) {
+    ItemBags b;
+    b.chunk = (int64_t)entry_stripe(e) * sc + j;
+    const int64_t per = (entry_quartered(e) ? kQuarterBagsPerRound : kRowBagsPerRound) * rounds;
+    b.first = b.chunk * per;
+    b.count = 0;
+    if (j >= sc || b.first >= batch) return b;
+    if (!entry_quartered(e) && b.chunk >= nchunks) return b;
+    b.count = batch - b.first < per ? batch - b.first : per;
+    return b;
+}
+
+// ---- host side.
 
 constexpr int kMaxEntries = 40;  // per XCD (kernel-argument size bound)
 constexpr int kMaxTables = 32;   // ET_MAX_TABLES_PER_LAUNCH
 
-inline uint32_t entry_table(uint32_t e) { return e & 0xffu; }
-
 // Stripe placement: which stripes XCD x owns.  Heavy tables (above light_bytes) -> stripe x on
 // XCD x, listed first; light tables' stripes laid out table after table (alternating large and
-// small tables) and cut into kXcds equal runs.  Returns the entries per XCD (= n).
+// small tables) and cut into kXcds equal runs.  A table of quarter_mask is quartered instead,
+// whatever its size: XCD x gets quarter x % 4 of batch half x / 4, one entry per XCD, in the
+// fabric class (with the heavy tables, in table order) or, with quarter_cache, at the front of the
+// cache class.  *nheavy is the size of the fabric class.  Returns the entries per XCD (= n).
 inline int place_stripes(const int64_t* table_bytes, int n, int64_t light_bytes,
+                         uint32_t quarter_mask, bool quarter_cache,
                          uint32_t entry[][kMaxEntries], int* nheavy) {
-    int heavy[kMaxTables], light[kMaxTables];
-    int nh = 0, nl = 0;
+    int heavy[kMaxTables], light[kMaxTables], qcache[kMaxTables];
+    int nh = 0, nl = 0, nq = 0;
+    auto quartered = [&](int t) { return ((quarter_mask >> t) & 1u) != 0; };
     for (int t = 0; t < n; ++t)
-        if (table_bytes[t] > light_bytes) heavy[nh++] = t;
+        if (quartered(t) && quarter_cache) qcache[nq++] = t;
+        else if (quartered(t) || table_bytes[t] > light_bytes) heavy[nh++] = t;
         else light[nl++] = t;
+    auto quarter_entry = [](int t, int x) {
+        return (uint32_t)t | ((uint32_t)(x / 4) << 8) | ((uint32_t)(x % 4) << 16) | kQuarterFlag;
+    };
     // light tables by size, then interleave large / small
     for (int a = 0; a < nl; ++a)
         for (int b = a + 1; b < nl; ++b)
@@ -87,8 +132,12 @@ inline int place_stripes(const int64_t* table_bytes, int n, int64_t light_bytes,
     int order[kMaxTables];
     for (int i = 0, lo = 0, hi = nl - 1; i < nl; ++i) order[i] = (i & 1) ? light[hi--] : light[lo++];
     int cnt[kXcds] = {0};
-    for (int x = 0; x < kXcds; ++x)
-        for (int h = 0; h < nh; ++h) entry[x][cnt[x]++] = (uint32_t)heavy[h] | ((uint32_t)x << 8);
+    for (int x = 0; x < kXcds; ++x) {
+        for (int h = 0; h < nh; ++h)
+            entry[x][cnt[x]++] = quartered(heavy[h]) ? quarter_entry(heavy[h], x)
+                                                     : (uint32_t)heavy[h] | ((uint32_t)x << 8);
+        for (int h = 0; h < nq; ++h) entry[x][cnt[x]++] = quarter_entry(qcache[h], x);
+    }
     // linear list of light stripes (order[i], st), st < kXcds; XCD x takes [x*nl, (x+1)*nl)
     for (int q = 0; q < nl * kXcds; ++q) {
         const int x = q / (nl > 0 ? nl : 1);
@@ -98,6 +147,11 @@ inline int place_stripes(const int64_t* table_bytes, int n, int64_t light_bytes,
     return cnt[0];
 }
 
+// No table quartered.
+inline int place_stripes(const int64_t* table_bytes, int n, int64_t light_bytes,
+                         uint32_t entry[][kMaxEntries], int* nheavy) {
+    return place_stripes(table_bytes, n, light_bytes, 0u, false, entry, nheavy);
+}
 // The order of an XCD's entries within a class (placement never changes: each function below
 // permutes e[0, n) in place).
 
