@@ -690,41 +690,23 @@ int launch_adagrad(const AdaRun& r, C eta, C eps) {
     return ET_OK;
 }
 
-}  // namespace et
-
-extern "C" int et_adagrad_workspace_size(const et_adagrad_desc* descs, int32_t ntables,
-                                         int64_t* bytes) {
-    et::clear_err();
-    if (!bytes) return et::fail(ET_ERR_ARG, "bytes is NULL");
-    int64_t n;
-    int pdim;
-    // sized for either form and any float type: only the sizes are read
-    const int rc = et::validate_adagrad(ET_F32, descs, ntables, true, &n, &pdim, false);
-    if (rc != ET_OK) return rc;
-    *bytes = et::carve_adagrad_ws(nullptr, n, pdim).bytes;
-    return ET_OK;
-}
-
-extern "C" int et_sparse_adagrad(int dtype, const et_adagrad_desc* descs, int32_t ntables,
-                                 double eta, double eps, uint32_t flags, void* workspace,
-                                 int64_t ws_bytes, void* stream) {
-    et::clear_err();
-    int rc = et::check_adagrad_call(dtype, flags);
-    if (rc != ET_OK) return rc;
-    const bool rowwise = (flags & ET_FLAG_ADAGRAD_ROWWISE) != 0;
-    et::AdaRun run;
-    rc = et::validate_adagrad(dtype, descs, ntables, rowwise, &run.n, &run.pdim, true);
+// The front of the pipeline, shared with et_weighted_adagrad: descriptor checks, the workspace,
+// the tables packed as vector or fixed-pool indices, the bag id of every ragged entry and
+// group_occurrences.  run.n == 0 on return means there is nothing to launch.
+inline int prepare_adagrad(int dtype, const et_adagrad_desc* descs, int ntables, bool rowwise,
+                           void* workspace, int64_t ws_bytes, void* stream, AdaRun& run) {
+    int rc = validate_adagrad(dtype, descs, ntables, rowwise, &run.n, &run.pdim, true);
     if (rc != ET_OK) return rc;
     if (run.n == 0) return ET_OK;
-    run.w = et::carve_adagrad_ws(static_cast<char*>(workspace), run.n, run.pdim);
+    run.w = carve_adagrad_ws(static_cast<char*>(workspace), run.n, run.pdim);
     if (!workspace || ws_bytes < run.w.bytes)
-        return et::fail(ET_ERR_WORKSPACE, "workspace of %lld bytes needed", (long long)run.w.bytes);
+        return fail(ET_ERR_WORKSPACE, "workspace of %lld bytes needed", (long long)run.w.bytes);
     run.ntables = ntables;
     run.s = static_cast<hipStream_t>(stream);
 
     // fixed-pool tables as they are, ragged ones as a vector index over their values
-    et::UpdatePack& pack = run.pack;
-    et::RaggedBagArgs ba{};
+    UpdatePack& pack = run.pack;
+    RaggedBagArgs ba{};
     uint32_t ro = 0, oo = 0;
     int64_t max_batch = 0;
     pack.vec_mask = 0;
@@ -732,7 +714,7 @@ extern "C" int et_sparse_adagrad(int dtype, const et_adagrad_desc* descs, int32_
     run.any_generic = false;
     for (int t = 0; t < ntables; ++t) {
         const et_adagrad_desc& a = descs[t];
-        const bool work = et::ada_work(a), ragged = et::ada_ragged(a);
+        const bool work = ada_work(a), ragged = ada_ragged(a);
         et_update_desc d{};
         d.table = a.table;
         d.ld_table = a.ld_table;
@@ -762,12 +744,12 @@ extern "C" int et_sparse_adagrad(int dtype, const et_adagrad_desc* descs, int32_
             if (a.batch > max_batch) max_batch = a.batch;
         }
         // the vector kernels: Float32 rows, gradient rows and state rows of 16-byte multiples
-        const bool vec = dtype == ET_F32 && (a.cols_per_page > 0 || et::aligned16(a.table)) &&
+        const bool vec = dtype == ET_F32 && (a.cols_per_page > 0 || aligned16(a.table)) &&
                          a.ld_table % 4 == 0 && a.dim % 4 == 0 && a.dim <= 2048 &&
-                         et::aligned16(a.delta) && a.ld_delta % 4 == 0 &&
+                         aligned16(a.delta) && a.ld_delta % 4 == 0 &&
                          (rowwise ? ((uintptr_t)a.state & 3u) == 0
-                                  : et::aligned16(a.state) && a.ld_state % 4 == 0);
-        if (vec && run.vg.add(et::vec_dim_ok(a.dim) ? a.dim : et::masked_capacity(a.dim), t))
+                                  : aligned16(a.state) && a.ld_state % 4 == 0);
+        if (vec && run.vg.add(vec_dim_ok(a.dim) ? a.dim : masked_capacity(a.dim), t))
             pack.vec_mask |= 1u << t;
         else
             run.any_generic = true;
@@ -778,11 +760,37 @@ extern "C" int et_sparse_adagrad(int dtype, const et_adagrad_desc* descs, int32_
 
     if (run.ap.ragged) {
         ET_HIP_CHECK(hipMemsetAsync(run.w.bag, 0, (size_t)run.n * 4, run.s));
-        rc = et::launch_ragged_bag_ids<uint32_t>(ba, ntables, max_batch, run.w.bag, run.s);
+        rc = launch_ragged_bag_ids<uint32_t>(ba, ntables, max_batch, run.w.bag, run.s);
         if (rc != ET_OK) return rc;
     }
-    rc = et::group_occurrences(pack, ntables, run.n, run.sent, et::kChunk, run.w.u, run.gr, run.s);
+    return group_occurrences(pack, ntables, run.n, run.sent, kChunk, run.w.u, run.gr, run.s);
+}
+
+}  // namespace et
+
+extern "C" int et_adagrad_workspace_size(const et_adagrad_desc* descs, int32_t ntables,
+                                         int64_t* bytes) {
+    et::clear_err();
+    if (!bytes) return et::fail(ET_ERR_ARG, "bytes is NULL");
+    int64_t n;
+    int pdim;
+    // sized for either form and any float type: only the sizes are read
+    const int rc = et::validate_adagrad(ET_F32, descs, ntables, true, &n, &pdim, false);
     if (rc != ET_OK) return rc;
+    *bytes = et::carve_adagrad_ws(nullptr, n, pdim).bytes;
+    return ET_OK;
+}
+
+extern "C" int et_sparse_adagrad(int dtype, const et_adagrad_desc* descs, int32_t ntables,
+                                 double eta, double eps, uint32_t flags, void* workspace,
+                                 int64_t ws_bytes, void* stream) {
+    et::clear_err();
+    int rc = et::check_adagrad_call(dtype, flags);
+    if (rc != ET_OK) return rc;
+    et::AdaRun run;
+    rc = et::prepare_adagrad(dtype, descs, ntables, (flags & ET_FLAG_ADAGRAD_ROWWISE) != 0,
+                             workspace, ws_bytes, stream, run);
+    if (rc != ET_OK || run.n == 0) return rc;
     return et::dispatch_adagrad(dtype, flags, [&](auto e, auto row, auto nt) {
         using T = typename decltype(e)::type;
         using C = typename decltype(e)::acc;

@@ -3756,6 +3756,9 @@ extern "C" int et_update_indexed(int dtype, void* table, int64_t ld_table,
 // Sparse AdaGrad (et_sparse_adagrad): kernels and entry points.
 #include "et_adagrad.hip"
 
+// Sparse AdaGrad over weighted gradients (et_weighted_adagrad): chunk kernels, entry points.
+#include "et_weighted_adagrad.hip"
+
 ET_OOB_READER(update)
 
 namespace et {

@@ -76,6 +76,8 @@ EXPORTS = (
     "et_weighted_sgd",
     "et_adagrad_workspace_size",
     "et_sparse_adagrad",
+    "et_weighted_adagrad_workspace_size",
+    "et_weighted_adagrad",
     "et_quantize_rows",
     "et_quant_maplookup_prealloc",
     "et_concat_slabs",
@@ -248,6 +250,12 @@ class AdaGradDesc(ctypes.Structure):
     ]
 
 
+class WeightedAdaGradDesc(ctypes.Structure):
+    """et_weighted_adagrad_desc (include/embtab.h): et_adagrad_desc and the weights."""
+
+    _fields_ = AdaGradDesc._fields_ + [("weights", ctypes.c_void_p)]
+
+
 class QuantDesc(ctypes.Structure):
     """et_quant_desc (include/embtab.h)."""
 
@@ -316,6 +324,8 @@ def load() -> ctypes.CDLL:
         "et_weighted_sgd": ([c_int, vp, i32, dbl, u32, vp, i64, vp], c_int),
         "et_adagrad_workspace_size": ([vp, i32, vp], c_int),
         "et_sparse_adagrad": ([c_int, vp, i32, dbl, dbl, u32, vp, i64, vp], c_int),
+        "et_weighted_adagrad_workspace_size": ([vp, i32, vp], c_int),
+        "et_weighted_adagrad": ([c_int, vp, i32, dbl, dbl, u32, vp, i64, vp], c_int),
         "et_quantize_rows": ([vp, i64, i64, i32, i32, vp, i64, vp, vp], c_int),
         "et_quant_maplookup_prealloc": ([c_int, vp, i32, i64, vp, i64, u32, vp], c_int),
         "et_concat_slabs": ([c_int, vp, i32, i64, i64, vp, vp, vp, i64, vp], c_int),

@@ -206,13 +206,20 @@ class AdaGrad:
     the table's storage.  It is allocated outside the C call, as ``device_table()`` is: call
     ``opt.state(A)`` (or run one eager step) before capturing ``update_`` into a HIP graph.
     ``set_state(table, tensor)`` installs a caller-owned tensor instead (a row block of a
-    wider one is fine: unit feature stride, any row stride >= D)."""
+    wider one is fine: unit feature stride, any row stride >= D).
+
+    ``weighted=True`` accepts gradients that carry ``weights`` (the pullback of a weighted or
+    mean-pooled lookup) and applies them through et_weighted_adagrad: a hot column is ordered
+    partial sums of ET_SGD_CHUNK entries, not the one serial chain of the weighted Descent.
+    An optimiser built without it refuses such a gradient with ``ArgumentError``, as it did
+    before that entry existed, so nothing that relied on the refusal changes."""
 
     def __init__(self, eta: float = 0.1, eps: float = 1e-8, rowwise: bool = False,
-                 initial_accumulator_value: float = 0.0):
+                 initial_accumulator_value: float = 0.0, weighted: bool = False):
         self.eta = float(eta)
         self.eps = float(eps)
         self.rowwise = bool(rowwise)
+        self.weighted = bool(weighted)
         self.initial_accumulator_value = float(initial_accumulator_value)
         self._state = weakref.WeakKeyDictionary()
 
@@ -620,11 +627,15 @@ def update_(*args, nontemporal: bool | None = None, exact: bool | None = None,
     ``weights[k] * delta[bag(k)]``, always the exact serial sum (``exact=False`` raises
     ``ArgumentError``; a hot column is one serial chain on one wave).  In a multi-table call
     such gradients are grouped into their own call per (path, eltype), ahead of the ragged
-    and the fixed-pool ones.  ``AdaGrad``, ``PhasedUpdate`` and the Indexer form refuse them.
+    and the fixed-pool ones.  ``PhasedUpdate``, the Indexer form and an ``AdaGrad`` built
+    without ``weighted=True`` refuse them.
 
     * ``update_(opt::AdaGrad, table, grad)`` and ``update_(opt::AdaGrad, tables, grads)`` —
       sparse AdaGrad (et_sparse_adagrad), fixed-pool and ragged gradients in the same call,
-      one call per element type and at most ET_MAX_TABLES_PER_LAUNCH tables.  ``nontemporal``
+      one call per element type and at most ET_MAX_TABLES_PER_LAUNCH tables.  With
+      ``AdaGrad(..., weighted=True)`` gradients that carry ``weights`` go through
+      et_weighted_adagrad, grouped the same way: a hot column is ordered partial sums of
+      ET_SGD_CHUNK entries, not one serial chain.  ``nontemporal``
       is its only keyword: ``exact``, ``hot_pass``, ``f16_fp32_acc``, ``indexer`` /
       ``indexers`` and ``telemetry_cb`` belong to the SGD and raise ``ArgumentError``."""
     for a in args[:2]:  # the table(s): first or second argument in every form
@@ -860,16 +871,41 @@ def _adagrad_desc(opt: AdaGrad, table, grad: SparseEmbeddingUpdate) -> _lib.AdaG
                             ld_state)
 
 
+def _weighted_adagrad_desc(opt: AdaGrad, table, grad: SparseEmbeddingUpdate):
+    """et_weighted_adagrad_desc of a gradient that carries weights: its indices in the ragged
+    form, checked as weighted_update_desc checks them for et_weighted_sgd."""
+    if table.dtype not in _UPDATE_DTYPES:
+        raise NotImplementedError(f"update of a {table.dtype} table")
+    r = grad.ragged()
+    if not r.is_cuda:
+        raise ArgumentError("indices must be in device memory")
+    u = weighted_update_desc(table, grad.delta, r, grad.weights.reshape(-1), None)
+    S = opt.state(table)
+    ld_state = 1 if opt.rowwise else (int(S.stride(0)) if S.shape[0] > 1 else int(S.shape[1]))
+    return _lib.WeightedAdaGradDesc(u.table, u.ld_table, u.nrows, u.dim, 1, u.delta, u.ld_delta,
+                                    u.idx, 1, u.batch, u.cols_per_page, u.colptr, u.nnz,
+                                    S.data_ptr(), ld_state, u.weights)
+
+
 def _update_adagrad(opt: AdaGrad, tables, grads, nontemporal: bool):
     """One et_sparse_adagrad call per element type and at most ET_MAX_TABLES_PER_LAUNCH
-    tables; fixed-pool and ragged gradients stay in the same call, empty ones are skipped."""
+    tables; fixed-pool and ragged gradients stay in the same call, empty ones are skipped.
+    Gradients that carry weights (a weighted or mean-pooled lookup) go through
+    et_weighted_adagrad in the same grouping, with workspaces of their own, if the optimiser
+    was built with ``weighted=True``; otherwise they are refused, as ever."""
     if len(tables) != len(grads):
         raise ArgumentError("tables and grads differ in length")
-    if any(g.weights is not None for g in grads):
-        raise ArgumentError("AdaGrad with a weighted gradient: weighted AdaGrad is not "
-                            "implemented (Descent only)")
+    if not opt.weighted and any(g.weights is not None for g in grads):
+        raise ArgumentError("AdaGrad with a weighted gradient: build the optimiser with "
+                            "weighted=True (et_weighted_adagrad)")
     groups: dict = {}
+    wgroups: dict = {}
     for A, g in zip(tables, grads):
+        if g.weights is not None:
+            d = _weighted_adagrad_desc(opt, A, g)
+            if d.nnz != 0 and d.batch != 0:
+                wgroups.setdefault(A.dtype, []).append(d)
+            continue
         I = g.indices
         if isinstance(I, RaggedIndices):
             if I.nnz == 0 or I.batch == 0:
@@ -893,6 +929,20 @@ def _update_adagrad(opt: AdaGrad, tables, grads, nontemporal: bool):
             _lib.check(L.et_sparse_adagrad(_lib.TORCH_TO_ET[dtype], ctypes.addressof(arr),
                                            len(part), opt.eta, opt.eps, flags, ws.data_ptr(),
                                            ws.numel(), _lib.stream_handle(dev)))
+            ncall += 1
+    ncall = 0
+    for dtype, descs in wgroups.items():
+        for c in range(0, len(descs), _lib.ET_MAX_TABLES_PER_LAUNCH):
+            part = descs[c:c + _lib.ET_MAX_TABLES_PER_LAUNCH]
+            arr = (_lib.WeightedAdaGradDesc * len(part))(*part)
+            nb = ctypes.c_int64(0)
+            _lib.check(L.et_weighted_adagrad_workspace_size(ctypes.addressof(arr), len(part),
+                                                            ctypes.byref(nb)))
+            dev = tables[0].device
+            ws = _workspace(nb.value, dev, f"weighted_adagrad{ncall}")
+            _lib.check(L.et_weighted_adagrad(_lib.TORCH_TO_ET[dtype], ctypes.addressof(arr),
+                                             len(part), opt.eta, opt.eps, flags, ws.data_ptr(),
+                                             ws.numel(), _lib.stream_handle(dev)))
             ncall += 1
 
 

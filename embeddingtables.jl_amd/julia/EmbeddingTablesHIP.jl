@@ -1008,18 +1008,84 @@ function update!(opt::SparseAdaGrad, table::HipTable{S,T}, grad::AdaGradUpdate,
     return _sparse_adagrad(T, opt, [_adagrad_desc(opt, table, grad)], Nontemporal)
 end
 
+# AdaGrad over a weighted gradient (et_weighted_adagrad; include/embtab.h "Sparse AdaGrad over
+# weighted gradients"): et_adagrad_desc and the weights.  A hot column is ordered partial sums
+# of ET_SGD_CHUNK entries, not the one serial chain of the weighted SGD.
+struct WeightedAdaGradDesc
+    table::Ptr{Cvoid}
+    ld_table::Int64
+    nrows::Int64
+    dim::Int32
+    pool::Int32
+    delta::Ptr{Cvoid}
+    ld_delta::Int64
+    idx::Ptr{Int64}
+    ld_idx::Int64
+    batch::Int64
+    cols_per_page::Int64
+    colptr::Ptr{Int64}
+    nnz::Int64
+    state::Ptr{Cvoid}
+    ld_state::Int64
+    weights::Ptr{Cvoid}
+end
+
+function _weighted_adagrad_desc(opt::SparseAdaGrad, A::HipTable{S,T},
+                                g::WeightedEmbeddingUpdate) where {S,T}
+    dp, dld = _ptr_ld(g.delta)
+    tp, ldt, cpp = _device_table(A)
+    R = g.indices
+    s = state(opt, A)
+    return WeightedAdaGradDesc(tp, ldt, size(A, 2), size(A, 1), 1, dp, dld, R.values.ptr, 1,
+                               batchsize(R), cpp, R.colptr.ptr, length(R.values),
+                               Ptr{Cvoid}(s.ptr), size(A, 1), _weights_ptr(T, g.weights))
+end
+
+function _weighted_adagrad(::Type{T}, opt::SparseAdaGrad, descs::Vector{WeightedAdaGradDesc},
+                           nontemporal::Bool) where {T}
+    isempty(descs) && return nothing
+    flags = (nontemporal ? ET_FLAG_NONTEMPORAL : UInt32(0)) |
+            (opt.rowwise ? ET_FLAG_ADAGRAD_ROWWISE : UInt32(0))
+    nb = Ref{Int64}(0)
+    check(ccall((:et_weighted_adagrad_workspace_size, libembtab), Cint,
+                (Ptr{WeightedAdaGradDesc}, Int32, Ref{Int64}), descs, length(descs), nb))
+    ws = _workspace(nb[], -3)
+    check(ccall((:et_weighted_adagrad, libembtab), Cint,
+                (Cint, Ptr{WeightedAdaGradDesc}, Int32, Float64, Float64, UInt32, Ptr{Cvoid},
+                 Int64, Ptr{Cvoid}),
+                et_dtype(T), descs, length(descs), opt.eta, opt.eps, flags, ws.ptr, length(ws),
+                stream()))
+    return nothing
+end
+
+function update!(opt::SparseAdaGrad, table::HipTable{S,T}, grad::WeightedEmbeddingUpdate,
+                 ::Val{Nontemporal} = Val(true)) where {S,T<:UpdateEltype,Nontemporal}
+    isempty(grad.indices) && return nothing
+    return _weighted_adagrad(T, opt, [_weighted_adagrad_desc(opt, table, grad)], Nontemporal)
+end
+
 # Fixed-pool and ragged gradients stay in one call: one call per element type and at most 32
-# tables (ET_MAX_TABLES_PER_LAUNCH); empty gradients are skipped.
+# tables (ET_MAX_TABLES_PER_LAUNCH); empty gradients are skipped.  Weighted gradients go
+# through et_weighted_adagrad, grouped the same way.
 function update!(opt::SparseAdaGrad, tables::AbstractVector{<:HipTable}, grads::AbstractVector,
                  ::Val{Nontemporal} = Val(true)) where {Nontemporal}
     length(tables) == length(grads) || throw(ArgumentError("tables and grads differ in length"))
     groups = Dict{DataType,Vector{AdaGradDesc}}()
+    wgroups = Dict{DataType,Vector{WeightedAdaGradDesc}}()
     for (A, g) in zip(tables, grads)
         isempty(g.indices) && continue
-        push!(get!(groups, eltype(A), AdaGradDesc[]), _adagrad_desc(opt, A, g))
+        if g isa WeightedEmbeddingUpdate
+            push!(get!(wgroups, eltype(A), WeightedAdaGradDesc[]),
+                  _weighted_adagrad_desc(opt, A, g))
+        else
+            push!(get!(groups, eltype(A), AdaGradDesc[]), _adagrad_desc(opt, A, g))
+        end
     end
     for (T, descs) in groups, c in 1:32:length(descs)
         _sparse_adagrad(T, opt, descs[c:min(c + 31, length(descs))], Nontemporal)
+    end
+    for (T, descs) in wgroups, c in 1:32:length(descs)
+        _weighted_adagrad(T, opt, descs[c:min(c + 31, length(descs))], Nontemporal)
     end
     return nothing
 end

@@ -565,6 +565,80 @@ int et_sparse_adagrad(int dtype, const et_adagrad_desc* descs, int32_t ntables, 
                       void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Sparse AdaGrad over weighted gradients: the pullback of a weighted or mean-pooled lookup.
+ * Everything of et_sparse_adagrad above holds (C, eta_c, eps_c, the element-wise and the
+ * row-wise form, every operation rounded once, nothing contracted, the state layout); only
+ * the gradient sum g of a table that carries weights differs.
+ *
+ * A weighted table is always in the ragged form: idx, colptr, the capacity nnz, the clamping
+ * and counting of et_ragged_desc.  A fixed-pool (B, P) index is the ragged index with
+ * colptr = 1 + P*(0:B).  `weights` has nnz entries of type C (Float32 for ET_F32 / ET_F16 /
+ * ET_BF16 tables, Float64 for ET_F64) and entry k of idx pairs with weights[k].
+ *
+ *   gradient sum g.  The column's list is its entries in increasing k, cut into consecutive
+ *   chunks of ET_SGD_CHUNK list positions.  Every chunk starts from p_c = +0; for every entry
+ *   of the chunk that a bag covers, in order:  t = C(w_k) * C(delta[:, bag(k)]);
+ *   p_c = p_c + t  (two roundings, never an fma).  g = p_0 for one chunk,
+ *   g = ((p_0 + p_1) + p_2) + ... in chunk order otherwise: et_sparse_adagrad's rule.
+ *
+ * An entry that no bag covers adds nothing but keeps its list position.  Nothing is read
+ * outside weights[0, nnz), and the value stored at an entry no bag covers never influences
+ * any result (it need not be a valid number).  A column is participating if at least one
+ * covered entry names it, WHATEVER that entry's weight: a weight of 0 still writes the column
+ * and its state.  0 * Inf and 0 * NaN are NaN, as in the special-values paragraph above;
+ * subnormal products are kept.
+ *
+ * Consequences (tests/test_gpu_weighted_adagrad.py pins them):
+ *   (a) with every covered weight 1.0, table and state equal et_sparse_adagrad on the same
+ *       ragged index bit for bit, element-wise and row-wise (the same g goes through the same
+ *       apply step);
+ *   (b) for ET_F32 / ET_F64 the result equals et_sparse_adagrad of the expanded gradient
+ *       E[:, k] = fl_C(w_k * delta[:, bag(k)]) with every covered entry its own bag (entries
+ *       in front of and behind the covered range stay uncovered by shifting colptr), bit for
+ *       bit;
+ *   (c) mean mode needs no entry of its own: its gradient carries w_k = 1 / len(bag(k)).
+ * ------------------------------------------------------------------------------- */
+
+/* One table of a weighted AdaGrad update: the fields of et_adagrad_desc, same order and
+ * meaning, and the weights. */
+typedef struct et_weighted_adagrad_desc {
+    void* table;           /* device pointer, updated in place */
+    int64_t ld_table;
+    int64_t nrows;
+    int32_t dim;
+    int32_t pool;          /* fixed pool (weights == NULL only); ignored when ragged */
+    const void* delta;     /* dim x batch gradient, column j at delta + j*ld_delta */
+    int64_t ld_delta;
+    const int64_t* idx;    /* fixed pool: the P x B indices; ragged: the values */
+    int64_t ld_idx;        /* fixed pool only */
+    int64_t batch;         /* bags (gradient columns) */
+    int64_t cols_per_page; /* as in et_lookup_desc */
+    const int64_t* colptr; /* NULL: a fixed pool.  Else batch + 1 entries, as et_ragged_desc */
+    int64_t nnz;           /* ragged: capacity of idx and of weights */
+    void* state;           /* as in et_adagrad_desc */
+    int64_t ld_state;      /* as in et_adagrad_desc */
+    const void* weights;   /* type C, nnz entries, or NULL */
+} et_weighted_adagrad_desc;
+
+/* Bytes of device workspace et_weighted_adagrad needs: et_adagrad_workspace_size of the same
+ * sizes (the weights are read in place, no copy of them is staged). */
+int et_weighted_adagrad_workspace_size(const et_weighted_adagrad_desc* descs, int32_t ntables,
+                                       int64_t* bytes);
+
+/* Sparse AdaGrad over gradients with a weight per entry (semantics above).  A table with
+ * weights == NULL behaves exactly as in et_sparse_adagrad, fixed-pool or ragged; one call may
+ * mix all three kinds.  weights != NULL with colptr == NULL is ET_ERR_ARG, and so are weights
+ * not aligned to C.  Every other check and flag rule is et_sparse_adagrad's, reported before
+ * any device work: ET_FLAG_NONTEMPORAL and ET_FLAG_ADAGRAD_ROWWISE are accepted, the SGD's
+ * flags return ET_ERR_UNSUPPORTED; a NULL state, ld_state < dim (element-wise), a state that
+ * overlaps its table, negative sizes and more than ET_MAX_TABLES_PER_LAUNCH tables are
+ * ET_ERR_ARG.  Stream-ordered on the caller's stream only, no allocation, no host
+ * synchronisation: capturable. */
+int et_weighted_adagrad(int dtype, const et_weighted_adagrad_desc* descs, int32_t ntables,
+                        double eta, double eps, uint32_t flags, void* workspace,
+                        int64_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Row-wise quantised tables (inference only): INT8 or INT4 rows with a per-row Float16 scale
  * and bias, dequantised inside the pooled sum — the layout of FBGEMM's Fused8BitRowwise /
  * FusedNBitRowwise with half-precision headers.  The reference has no quantised table; the

@@ -104,7 +104,7 @@ def parse_notes(text: str) -> list:
         if cur is None:
             continue
         if key in ("agpr_count", "vgpr_count", "sgpr_count", "group_segment_fixed_size",
-                   "private_segment_fixed_size"):
+                   "private_segment_fixed_size", "kernarg_segment_size"):
             cur[key] = int(val)
         elif key in ("name", "symbol"):
             cur.setdefault(key, val.strip("'\""))

@@ -13,8 +13,9 @@ For a change that must not touch device code (a refactor of the host side, a rem
 dead variants): the kernel symbols of NEW must be those of OLD minus the ones containing a
 REMOVED_SUBSTRING, and every remaining kernel must keep its registers, LDS, private segment
 and its disassembly.  Only what depends on where a kernel sits in its code object is
-normalised: the address column and comments, and the literal of the s_add_u32 / s_addc_u32
-pair that follows an s_getpc_b64.  Exit status 1 and a list of what differs otherwise."""
+normalised: the address column and comments, the "..." that objdump prints for zero padding
+behind a kernel, and the literal of the s_add_u32 / s_addc_u32 pair that follows an
+s_getpc_b64.  Exit status 1 and a list of what differs otherwise."""
 import collections
 import os
 import re
@@ -31,7 +32,7 @@ def normalise(text: str) -> list:
     out, pc = [], 0
     for line in text.splitlines():
         s = re.sub(r"^\s*[0-9a-f]+:\s+", "", line.split("//")[0]).strip()
-        if not s:
+        if not s or s == "...":  # "...": objdump's mark for zero padding behind a kernel
             continue
         if s.startswith("s_getpc_b64"):
             pc = 3  # the two instructions that follow: the s_add_u32 / s_addc_u32 pair
