@@ -3759,6 +3759,9 @@ extern "C" int et_update_indexed(int dtype, void* table, int64_t ld_table,
 // Sparse AdaGrad over weighted gradients (et_weighted_adagrad): chunk kernels, entry points.
 #include "et_weighted_adagrad.hip"
 
+// Split sparse SGD over ragged and weighted gradients (et_ragged_sgd_split): kernels, entries.
+#include "et_ragged_sgd_split.hip"
+
 ET_OOB_READER(update)
 
 namespace et {

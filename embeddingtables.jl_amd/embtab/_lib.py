@@ -78,6 +78,8 @@ EXPORTS = (
     "et_sparse_adagrad",
     "et_weighted_adagrad_workspace_size",
     "et_weighted_adagrad",
+    "et_ragged_sgd_split_workspace_size",
+    "et_ragged_sgd_split",
     "et_quantize_rows",
     "et_quant_maplookup_prealloc",
     "et_concat_slabs",
@@ -326,6 +328,8 @@ def load() -> ctypes.CDLL:
         "et_sparse_adagrad": ([c_int, vp, i32, dbl, dbl, u32, vp, i64, vp], c_int),
         "et_weighted_adagrad_workspace_size": ([vp, i32, vp], c_int),
         "et_weighted_adagrad": ([c_int, vp, i32, dbl, dbl, u32, vp, i64, vp], c_int),
+        "et_ragged_sgd_split_workspace_size": ([vp, i32, vp], c_int),
+        "et_ragged_sgd_split": ([c_int, vp, i32, dbl, u32, vp, i64, vp], c_int),
         "et_quantize_rows": ([vp, i64, i64, i32, i32, vp, i64, vp, vp], c_int),
         "et_quant_maplookup_prealloc": ([c_int, vp, i32, i64, vp, i64, u32, vp], c_int),
         "et_concat_slabs": ([c_int, vp, i32, i64, i64, vp, vp, vp, i64, vp], c_int),

@@ -562,6 +562,49 @@ def _defer_weighted(indexer, grad: "SparseEmbeddingUpdate", maxindex: int):
         indexer._pending = (I.clone(), int(maxindex))
 
 
+def _is_split_grad(grad: "SparseEmbeddingUpdate") -> bool:
+    """The gradients ``split=True`` routes through et_ragged_sgd_split: ragged ones and every
+    one that carries weights."""
+    return grad.weights is not None or isinstance(grad.indices, RaggedIndices)
+
+
+def _split_grad_desc(table, grad: "SparseEmbeddingUpdate") -> _lib.WeightedUpdateDesc:
+    """et_weighted_update_desc of a ragged or weighted gradient for et_ragged_sgd_split
+    (weights NULL: an unweighted ragged gradient)."""
+    if table.dtype not in _UPDATE_DTYPES:
+        raise NotImplementedError(f"update of a {table.dtype} table")
+    if grad.weights is None:
+        r = _check_idx(grad.indices)
+        return weighted_update_desc(table, grad.delta, r, None, None)
+    r = grad.ragged()
+    if not r.is_cuda:
+        raise ArgumentError("indices must be in device memory")
+    return weighted_update_desc(table, grad.delta, r, grad.weights.reshape(-1), None)
+
+
+def _defer_split(indexer, grad: "SparseEmbeddingUpdate", maxindex: int):
+    """Fill a caller's Indexer as the exact weighted and ragged paths do."""
+    if grad.weights is not None:
+        _defer_weighted(indexer, grad, maxindex)
+    elif isinstance(indexer, Indexer):
+        indexer._defer_ragged(grad.indices, maxindex)
+
+
+def _ragged_sgd_split(descs, eta: float, flags: int, device, dtype,
+                      key: str = "ragged_sgd_split"):
+    """One et_ragged_sgd_split call over ragged and weighted gradients (hot columns as ordered
+    partial sums of ET_SGD_CHUNK entries; caller's stream only)."""
+    L = _lib.load()
+    n = len(descs)
+    arr = (_lib.WeightedUpdateDesc * n)(*descs)
+    nb = ctypes.c_int64(0)
+    _lib.check(L.et_ragged_sgd_split_workspace_size(ctypes.addressof(arr), n, ctypes.byref(nb)))
+    ws = _workspace(nb.value, device, key)
+    _lib.check(L.et_ragged_sgd_split(_lib.TORCH_TO_ET[dtype], ctypes.addressof(arr), n,
+                                     float(eta), flags, ws.data_ptr(), ws.numel(),
+                                     _lib.stream_handle(device)))
+
+
 def _sparse_sgd(descs, eta: float, flags: int, device, dtype=torch.float32, snaps=None):
     """One et_sparse_sgd call; `snaps` (one device pointer or None per descriptor) makes it
     et_sparse_sgd_snap, whose key pass copies those tables' index arrays."""
@@ -595,7 +638,7 @@ EXACT_DEFAULT = None
 
 
 def update_(*args, nontemporal: bool | None = None, exact: bool | None = None,
-            f16_fp32_acc: bool = False, hot_pass: bool = False, **kw):
+            f16_fp32_acc: bool = False, hot_pass: bool = False, split: bool = False, **kw):
     """Julia's ``update!`` (multiple dispatch on the argument types):
 
     * ``update_(opt::Descent, table, grad, [indexer], [nontemporal])`` — single table,
@@ -630,20 +673,36 @@ def update_(*args, nontemporal: bool | None = None, exact: bool | None = None,
     and the fixed-pool ones.  ``PhasedUpdate``, the Indexer form and an ``AdaGrad`` built
     without ``weighted=True`` refuse them.
 
+    ``split=True`` (opt-in, ``Descent`` only) is the split mode of those two kinds: every
+    ragged gradient and every gradient that carries weights (weighted or mean-pooled,
+    fixed-pool ``WeightedIndices`` included) goes through et_ragged_sgd_split, in which a
+    column of more than ET_SGD_CHUNK list positions is summed as ordered partial sums of
+    ET_SGD_CHUNK entries (the chunk rule of et_weighted_adagrad) instead of one serial chain on
+    one wave: deterministic, bit-identical to the exact paths for every shorter column, not the
+    reference's order for a hot one.  Float16 sums are Float32 (``f16_fp32_acc`` is implied).
+    In a multi-table call such gradients are grouped per (path, eltype) into calls of at most
+    ET_MAX_TABLES_PER_LAUNCH tables, weighted and unweighted ones together, each with a
+    workspace of its own, ahead of the fixed-pool unweighted gradients, which follow ``exact``
+    as ever; Indexers are filled and ``telemetry_cb`` runs as on the exact paths.
+    ``split=True`` with ``exact=True`` or ``hot_pass=True`` raises ``ArgumentError``;
+    ``exact=False`` and ``exact=None`` are fine.  With ``split=False``, the default, nothing
+    changes: a ragged gradient with ``exact=False`` stays exact and a weighted one raises.
+
     * ``update_(opt::AdaGrad, table, grad)`` and ``update_(opt::AdaGrad, tables, grads)`` —
       sparse AdaGrad (et_sparse_adagrad), fixed-pool and ragged gradients in the same call,
       one call per element type and at most ET_MAX_TABLES_PER_LAUNCH tables.  With
       ``AdaGrad(..., weighted=True)`` gradients that carry ``weights`` go through
       et_weighted_adagrad, grouped the same way: a hot column is ordered partial sums of
       ET_SGD_CHUNK entries, not one serial chain.  ``nontemporal``
-      is its only keyword: ``exact``, ``hot_pass``, ``f16_fp32_acc``, ``indexer`` /
+      is its only keyword: ``exact``, ``hot_pass``, ``f16_fp32_acc``, ``split``, ``indexer`` /
       ``indexers`` and ``telemetry_cb`` belong to the SGD and raise ``ArgumentError``."""
     for a in args[:2]:  # the table(s): first or second argument in every form
         if isinstance(a, (AbstractEmbeddingTable, list, tuple)):
             refuse_quantized(a, "update_")
     if args and isinstance(args[0], AdaGrad):
         refused = {"exact": exact is not None, "f16_fp32_acc": bool(f16_fp32_acc),
-                   "hot_pass": bool(hot_pass), "indexer / indexers (positional)": len(args) > 3}
+                   "hot_pass": bool(hot_pass), "split": bool(split),
+                   "indexer / indexers (positional)": len(args) > 3}
         refused.update({k: True for k in kw})
         for name, given in refused.items():
             if given:
@@ -657,6 +716,15 @@ def update_(*args, nontemporal: bool | None = None, exact: bool | None = None,
         else:
             _update_adagrad(args[0], list(args[1]), list(args[2]), nt)
         return None
+    if split:
+        if not (args and isinstance(args[0], Descent)):
+            raise ArgumentError("split=True belongs to update_(opt::Descent, ...)")
+        if exact:
+            raise ArgumentError("split=True with exact=True: the split update is the opposite "
+                                "of the exact serial sum")
+        if hot_pass:
+            raise ArgumentError("split=True with hot_pass=True: et_ragged_sgd_split has no "
+                                "hot-column pass")
     if exact is None:
         exact = EXACT_DEFAULT
     if args and isinstance(args[0], Descent):
@@ -665,13 +733,15 @@ def update_(*args, nontemporal: bool | None = None, exact: bool | None = None,
             table, grad = args[1], args[2]
             nt = args[4] if len(args) > 4 else (True if nontemporal is None else nontemporal)
             indexer = args[3] if len(args) > 3 else kw.get("indexer")
-            _update_single(opt, table, grad, nt, exact, f16_fp32_acc, hot_pass, indexer)
+            _update_single(opt, table, grad, nt, exact, f16_fp32_acc, hot_pass, indexer,
+                           bool(split))
             return None
         tables, grads = list(args[1]), list(args[2])
         nt = args[4] if len(args) > 4 else (True if nontemporal is None else nontemporal)
         if len(args) > 3 and args[3] is not None:
             kw["indexers"] = args[3]
-        _update_multi(opt, tables, grads, nt, exact, f16_fp32_acc, hot_pass=hot_pass, **kw)
+        _update_multi(opt, tables, grads, nt, exact, f16_fp32_acc, hot_pass=hot_pass,
+                      split=bool(split), **kw)
         return None
     table, grad, indexer, alpha = args[:4]
     nt = args[4] if len(args) > 4 else (True if nontemporal is None else nontemporal)
@@ -681,11 +751,21 @@ def update_(*args, nontemporal: bool | None = None, exact: bool | None = None,
 
 def _update_single(opt: Descent, table, grad: SparseEmbeddingUpdate, nontemporal: bool,
                    exact: bool, f16_fp32_acc: bool = False, hot_pass: bool = False,
-                   indexer=None):
+                   indexer=None, split: bool = False):
     """src/sparseupdate.jl:159-178: ``index!(indexer, update.indices, size(table, 2))``, then
     the update from it.  The device pipeline indexes on its own; a caller-supplied Indexer is
     filled as the reference's is, from a snapshot of the indices the update's key pass takes
     (et_sparse_sgd_snap), built into the reference layout on first use (Indexer._defer)."""
+    if split and _is_split_grad(grad):
+        # ragged or weighted gradient, split mode: et_ragged_sgd_split
+        d = _split_grad_desc(table, grad)
+        _defer_split(indexer, grad, table.size()[1])
+        if d.nnz == 0 or d.batch == 0:
+            return
+        _ragged_sgd_split([d], opt.eta, _sgd_flags(fused_update_path(table), nontemporal, False,
+                                                   False, f16_fp32_acc),
+                          table.device, table.dtype)
+        return
     if grad.weights is not None:
         # weighted gradient (a weighted or mean-pooled lookup): et_weighted_sgd
         d = _weighted_grad_desc(table, grad, exact)
@@ -722,7 +802,8 @@ def _update_single(opt: Descent, table, grad: SparseEmbeddingUpdate, nontemporal
 
 def _update_multi(opt: Descent, tables, grads, nontemporal: bool, exact: bool | None,
                   f16_fp32_acc: bool = False, num_splits=4, nthreads=None, scratchspaces=None,
-                  telemetry_cb=None, indexers=None, hot_pass: bool = False):
+                  telemetry_cb=None, indexers=None, hot_pass: bool = False,
+                  split: bool = False):
     """src/sparseupdate.jl:199-238: index every table, ``telemetry_cb()``, then update
     every table.  Both phases are one device pipeline per (path, eltype) group of at
     most ET_MAX_TABLES_PER_LAUNCH tables; with a ``telemetry_cb`` they are two calls
@@ -739,6 +820,33 @@ def _update_multi(opt: Descent, tables, grads, nontemporal: bool, exact: bool | 
         indexers = list(indexers)
         if len(indexers) != len(grads):
             raise ArgumentError("indexers and grads differ in length")
+    spl = [i for i, g in enumerate(grads) if split and _is_split_grad(g)]
+    if spl:
+        # split mode: the ragged and the weighted gradients together, one et_ragged_sgd_split
+        # call per (path, eltype) group, ahead of the fixed-pool unweighted ones, which take
+        # the usual path and follow `exact`
+        sgroups: dict = {}
+        for i in spl:
+            A, g = tables[i], grads[i]
+            d = _split_grad_desc(A, g)
+            if indexers is not None:
+                _defer_split(indexers[i], g, A.size()[1])
+            if d.nnz == 0 or d.batch == 0:
+                continue
+            sgroups.setdefault((fused_update_path(A), A.dtype), []).append(d)
+        ncall = 0
+        for (fused, dtype), descs in sgroups.items():
+            for c in range(0, len(descs), _lib.ET_MAX_TABLES_PER_LAUNCH):
+                _ragged_sgd_split(descs[c:c + _lib.ET_MAX_TABLES_PER_LAUNCH], opt.eta,
+                                  _sgd_flags(fused, nontemporal, not fused, False, f16_fp32_acc),
+                                  tables[0].device, dtype, f"ragged_sgd_split{ncall}")
+                ncall += 1
+        rest = [i for i in range(len(grads)) if i not in set(spl)]
+        return _update_multi(opt, [tables[i] for i in rest], [grads[i] for i in rest],
+                             nontemporal, exact, f16_fp32_acc, num_splits, nthreads,
+                             scratchspaces, telemetry_cb,
+                             None if indexers is None else [indexers[i] for i in rest],
+                             hot_pass)
     wtd = [i for i, g in enumerate(grads) if g.weights is not None]
     if wtd:
         # gradients that carry weights: their own et_weighted_sgd call per (path, eltype)

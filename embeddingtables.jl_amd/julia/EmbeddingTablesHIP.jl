@@ -766,18 +766,25 @@ function _ragged_sgd(::Type{T}, descs::Vector{RaggedUpdateDesc}, eta::Float64,
                 et_dtype(T), descs, length(descs), eta, flags, ws.ptr, length(ws), stream()))
 end
 
-# A ragged gradient: delta (D x batch) and the RaggedIndices of the forward lookup.  Always
-# the exact serial sum (et_ragged_sgd never splits a column).
+# A ragged gradient: delta (D x batch) and the RaggedIndices of the forward lookup.  The
+# exact serial sum by default (et_ragged_sgd never splits a column); `split = true` sums a
+# column of more than ET_SGD_CHUNK entries as ordered partial sums (et_ragged_sgd_split).
 struct RaggedEmbeddingUpdate{D}
     delta::D
     indices::RaggedIndices
 end
 
 function update!(opt::Flux.Descent, table::HipTable{S,T}, grad::RaggedEmbeddingUpdate,
-                 ::Val{Nontemporal} = Val(true)) where {S,T<:UpdateEltype,Nontemporal}
+                 ::Val{Nontemporal} = Val(true);
+                 split::Bool = false) where {S,T<:UpdateEltype,Nontemporal}
     isempty(grad.indices) && return nothing
     flags = (Nontemporal ? ET_FLAG_NONTEMPORAL : UInt32(0)) |
             (_fused(table) ? UInt32(0) : ET_FLAG_SGD_UNFUSED)
+    if split
+        descs = [_weighted_update_desc(table, grad.delta, grad.indices, nothing, nothing)]
+        _ragged_sgd_split(T, descs, Float64(opt.eta), flags)
+        return nothing
+    end
     dp, dld = _ptr_ld(grad.delta)
     tp, ldt, cpp = _device_table(table)
     R = grad.indices
@@ -898,12 +905,31 @@ function weight_grad(table::HipTable{S,T}, delta, R::RaggedIndices) where {S,T<:
     return dw
 end
 
+# The split sparse SGD over ragged and weighted gradients (weights NULL: unweighted): a hot
+# column is ordered partial sums of ET_SGD_CHUNK entries, not one serial chain.
+function _ragged_sgd_split(::Type{T}, descs::Vector{WeightedUpdateDesc}, eta::Float64,
+                           flags::UInt32) where {T}
+    nb = Ref{Int64}(0)
+    check(ccall((:et_ragged_sgd_split_workspace_size, libembtab), Cint,
+                (Ptr{WeightedUpdateDesc}, Int32, Ref{Int64}), descs, length(descs), nb))
+    ws = _workspace(nb[], -4)
+    check(ccall((:et_ragged_sgd_split, libembtab), Cint,
+                (Cint, Ptr{WeightedUpdateDesc}, Int32, Float64, UInt32, Ptr{Cvoid}, Int64,
+                 Ptr{Cvoid}),
+                et_dtype(T), descs, length(descs), eta, flags, ws.ptr, length(ws), stream()))
+end
+
 function update!(opt::Flux.Descent, table::HipTable{S,T}, grad::WeightedEmbeddingUpdate,
-                 ::Val{Nontemporal} = Val(true)) where {S,T<:UpdateEltype,Nontemporal}
+                 ::Val{Nontemporal} = Val(true);
+                 split::Bool = false) where {S,T<:UpdateEltype,Nontemporal}
     isempty(grad.indices) && return nothing
     flags = (Nontemporal ? ET_FLAG_NONTEMPORAL : UInt32(0)) |
             (_fused(table) ? UInt32(0) : ET_FLAG_SGD_UNFUSED)
     descs = [_weighted_update_desc(table, grad.delta, grad.indices, grad.weights, nothing)]
+    if split
+        _ragged_sgd_split(T, descs, Float64(opt.eta), flags)
+        return nothing
+    end
     nb = Ref{Int64}(0)
     check(ccall((:et_weighted_sgd_workspace_size, libembtab), Cint,
                 (Ptr{WeightedUpdateDesc}, Int32, Ref{Int64}), descs, length(descs), nb))

@@ -639,6 +639,68 @@ int et_weighted_adagrad(int dtype, const et_weighted_adagrad_desc* descs, int32_
                         int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------
+ * Split sparse SGD over ragged and weighted gradients: the opt-in counterpart of
+ * et_ragged_sgd and et_weighted_sgd for skewed data.  Those two sum every column as one serial
+ * chain on one wave; here a hot column is ordered partial sums of ET_SGD_CHUNK entries, as in
+ * et_weighted_adagrad, followed by the update of et_sparse_sgd.  Deterministic; NOT the
+ * reference's serial order for a column of more than ET_SGD_CHUNK list positions.
+ *
+ * Tables are et_weighted_update_desc: always the ragged form (idx, colptr, the capacity nnz,
+ * the clamping and counting of et_ragged_desc).  weights == NULL is an unweighted ragged
+ * gradient, otherwise `weights` has nnz entries of type C; one call may mix both kinds.
+ * dweights is ignored.  C is Float32 for ET_F32 / ET_F16 / ET_BF16 tables (ET_FLAG_F16_FP32_ACC
+ * is implied and accepted, as in et_weighted_sgd) and Float64 for ET_F64.
+ *
+ *   gradient sum g of a participating column: et_weighted_adagrad's rule, word for word.  The
+ *   column's list is its entries in increasing k, cut into consecutive chunks of ET_SGD_CHUNK
+ *   list positions.  Every chunk starts from p_c = +0; for every entry of the chunk that a bag
+ *   covers, in order:  t = C(w_k) * C(delta[:, bag(k)]);  p_c = p_c + t  (two roundings, never
+ *   an fma; a table without weights does no product at all: p_c = p_c + C(delta[:, bag(k)])).
+ *   g = p_0 for one chunk, g = ((p_0 + p_1) + p_2) + ... in chunk order otherwise.
+ *
+ *   apply step: et_sparse_sgd's.  Fused (default): fma(-eta_c, g, w) in C, then one rounding
+ *   to T;  ET_FLAG_SGD_UNFUSED: w - eta_c*g with two roundings;  ET_FLAG_SGD_UNFUSED |
+ *   ET_FLAG_SGD_F64_ALPHA: evaluated in Float64 with the unconverted eta.
+ *
+ * An entry that no bag covers adds nothing but keeps its list position, and its weight is never
+ * read.  A column participates if at least one covered entry names it, whatever that entry's
+ * weight (a weight of 0 still writes the column; 0 * Inf is NaN); a column with no
+ * participating entry is not written.  An index outside 1..nrows is counted (et_check_errors)
+ * and writes nothing; colptr bounds are clamped and counted as in et_ragged_desc.
+ *
+ * Consequences (tests/test_gpu_ragged_split.py pins them):
+ *   (a) a column of at most ET_SGD_CHUNK list positions gets the result of et_ragged_sgd or
+ *       et_weighted_sgd bit for bit (for ET_F16: et_ragged_sgd with ET_FLAG_F16_FP32_ACC);
+ *   (b) with every covered weight 1.0 the result equals weights == NULL bit for bit;
+ *   (c) for ET_F32 / ET_F64 the result equals the same call on the expanded gradient
+ *       E[:, k] = fl_C(w_k * delta[:, bag(k)]) with every covered entry its own bag and no
+ *       weights, bit for bit;
+ *   (d) mean mode needs nothing of its own: its gradient carries w_k = 1 / len(bag(k)).
+ * ------------------------------------------------------------------------------- */
+
+/* Bytes of device workspace et_ragged_sgd_split needs: et_weighted_adagrad_workspace_size of
+ * the same sizes (the index workspace, a bag id per entry, the partial rows and their
+ * participation flags; the weights are read in place). */
+int et_ragged_sgd_split_workspace_size(const et_weighted_update_desc* descs, int32_t ntables,
+                                       int64_t* bytes);
+
+/* Split sparse SGD over ragged and weighted gradients (semantics above).  ET_F32 / ET_F64 /
+ * ET_F16 / ET_BF16; anything else returns ET_ERR_UNSUPPORTED.  Flags: ET_FLAG_NONTEMPORAL (the
+ * row stores), ET_FLAG_SGD_UNFUSED and ET_FLAG_SGD_F64_ALPHA select the apply step;
+ * ET_FLAG_F16_FP32_ACC and ET_FLAG_EXACT_IF_FAST are accepted and change nothing;
+ * ET_FLAG_EXACT_UPDATE is ET_ERR_ARG (the call is the opposite of exact);
+ * ET_FLAG_SGD_INDEX_ONLY, ET_FLAG_SGD_APPLY_ONLY, ET_FLAG_SGD_HOT_PASS and
+ * ET_FLAG_ADAGRAD_ROWWISE return ET_ERR_UNSUPPORTED.  ET_ERR_ARG before any device work: every
+ * descriptor check of et_weighted_sgd except the NULL weights (NULL table, delta, idx or
+ * colptr of a table with work, negative sizes, a leading dimension below dim, too many tables)
+ * and weights not aligned to C.  Stream-ordered on the caller's stream only: no side streams,
+ * no allocation, no host synchronisation, capturable.  The sum of nnz must stay below
+ * 2^31 - 1. */
+int et_ragged_sgd_split(int dtype, const et_weighted_update_desc* descs, int32_t ntables,
+                        double eta, uint32_t flags, void* workspace, int64_t ws_bytes,
+                        void* stream);
+
+/* ---------------------------------------------------------------------------------
  * Row-wise quantised tables (inference only): INT8 or INT4 rows with a per-row Float16 scale
  * and bias, dequantised inside the pooled sum — the layout of FBGEMM's Fused8BitRowwise /
  * FusedNBitRowwise with half-precision headers.  The reference has no quantised table; the
