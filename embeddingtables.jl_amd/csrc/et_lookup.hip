@@ -1714,6 +1714,9 @@ ET_OOB_READER(lookup)
 // Row-wise quantised tables (et_quantize_rows, et_quant_maplookup_prealloc).
 #include "et_quant.hip"
 
+// FP8 rows (et_fp8_quantize_rows, et_fp8_maplookup_prealloc).
+#include "et_fp8.hip"
+
 #ifdef ET_WG_TIMELINE
 // Profiling build only: copies the striped launch's workgroup records (2 x uint4 each)
 // to host memory; returns the number copied.

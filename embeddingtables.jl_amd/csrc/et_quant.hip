@@ -406,27 +406,38 @@ inline int quant_lpr(int64_t vpr) {
     return c;
 }
 
-template <int BITS, int LPR>
-int launch_quant_vec(const QuantPack& pack, int n, int64_t batch, void* dst, int64_t ld_dst,
-                     int out, bool nt, hipStream_t s) {
-    const int64_t per = 4 * QuantGeom<BITS, LPR>::GPW;
-    const int64_t nchunks = (batch + per - 1) / per;
-    const int64_t stripe_chunks = (nchunks + kXcds - 1) / kXcds;
-    const int64_t grid = (int64_t)kXcds * n * stripe_chunks;
-    if (grid > 0x7fffffffll) return fail(ET_ERR_ARG, "grid too large");
+// The grid of a vector launch (`per` bags a workgroup) and the stripe entries of its XCDs.
+struct QuantGrid {
+    int64_t grid, stripe_chunks, nchunks;
+    QuantStripes sm;
+};
+
+inline int quant_vec_grid(const QuantPack& pack, int n, int64_t batch, int64_t per, QuantGrid* g) {
+    g->nchunks = (batch + per - 1) / per;
+    g->stripe_chunks = (g->nchunks + kXcds - 1) / kXcds;
+    g->grid = (int64_t)kXcds * n * g->stripe_chunks;
+    if (g->grid > 0x7fffffffll) return fail(ET_ERR_ARG, "grid too large");
     int64_t bytes[ET_MAX_TABLES_PER_LAUNCH];
     for (int t = 0; t < n; ++t) bytes[t] = pack.d[t].nrows * pack.d[t].ld_bytes;
     uint32_t entry[kXcds][et_order::kMaxEntries];
     int nheavy = 0;
     const int nent = et_order::place_stripes(bytes, n, tuning().light_bytes, entry, &nheavy);
     if (nent != n) return fail(ET_ERR_HIP, "stripe placement gave %d entries for %d tables", nent, n);
-    QuantStripes sm;
-    memset(&sm, 0, sizeof(sm));
+    memset(&g->sm, 0, sizeof(g->sm));
     for (int x = 0; x < kXcds; ++x)
         for (int k = 0; k < n; ++k)
-            sm.e[x][k] = (uint8_t)((entry[x][k] & 31u) | (((entry[x][k] >> 8) & 7u) << 5));
-    hipLaunchKernelGGL((k_quant_vec<BITS, LPR>), dim3((unsigned)grid), dim3(256), 0, s, pack, sm, n,
-                       batch, dst, ld_dst, out, nt ? 1 : 0, stripe_chunks, nchunks);
+            g->sm.e[x][k] = (uint8_t)((entry[x][k] & 31u) | (((entry[x][k] >> 8) & 7u) << 5));
+    return ET_OK;
+}
+
+template <int BITS, int LPR>
+int launch_quant_vec(const QuantPack& pack, int n, int64_t batch, void* dst, int64_t ld_dst,
+                     int out, bool nt, hipStream_t s) {
+    QuantGrid g;
+    const int rc = quant_vec_grid(pack, n, batch, 4 * QuantGeom<BITS, LPR>::GPW, &g);
+    if (rc != ET_OK) return rc;
+    hipLaunchKernelGGL((k_quant_vec<BITS, LPR>), dim3((unsigned)g.grid), dim3(256), 0, s, pack,
+                       g.sm, n, batch, dst, ld_dst, out, nt ? 1 : 0, g.stripe_chunks, g.nchunks);
     ET_LAUNCH_CHECK("k_quant_vec");
     return ET_OK;
 }
@@ -457,10 +468,13 @@ int launch_quant_generic(const QuantPack& pack, int n, int64_t batch, void* dst,
     return ET_OK;
 }
 
-// Validate (everything before any device work), group the tables by kernel and launch one
-// kernel per group: key 0 = generic, else bits * 256 + lane-group capacity.
-inline int quant_dispatch(int out, const et_quant_desc* descs, int ntables, int64_t batch,
-                          void* dst, int64_t ld_dst, uint32_t flags, hipStream_t s) {
+// Validate (everything before any device work) and key every table by its kernel: -1 nothing
+// to do, 0 = generic, else bits * 256 + lane-group capacity.  `only_bits` != 0 (the FP8 entry)
+// refuses every other width.  *work = false: the call is a no-op.
+inline int quant_validate(int out, const et_quant_desc* descs, int ntables, int64_t batch,
+                          const void* dst, int64_t ld_dst, uint32_t flags, int only_bits,
+                          int (&key_of)[ET_MAX_TABLES_PER_LAUNCH], bool* work) {
+    *work = false;
     if (out != ET_F32 && out != ET_F16 && out != ET_BF16)
         return fail(ET_ERR_UNSUPPORTED, "destination dtype %d (Float32, Float16 or BFloat16)", out);
     if (flags & ~ET_FLAG_NONTEMPORAL)
@@ -472,9 +486,10 @@ inline int quant_dispatch(int out, const et_quant_desc* descs, int ntables, int6
     if (batch >= 0x7fffffffll) return fail(ET_ERR_ARG, "batch too large");
     if (!descs) return fail(ET_ERR_ARG, "descs is NULL");
     if (!dst) return fail(ET_ERR_ARG, "dst is NULL");
-    int key_of[ET_MAX_TABLES_PER_LAUNCH];  // -1 nothing to do
     for (int t = 0; t < ntables; ++t) {
         const et_quant_desc& d = descs[t];
+        if (only_bits && d.bits != only_bits)
+            return fail(ET_ERR_ARG, "table %d: bits %d, this entry takes %d", t, d.bits, only_bits);
         int64_t payload = 0;
         const int rc = quant_row_check("table", t, d.dim, d.bits, d.ld_bytes, d.hdr == nullptr,
                                        &payload);
@@ -501,8 +516,14 @@ inline int quant_dispatch(int out, const et_quant_desc* descs, int ntables, int6
                          d.nrows > 0 && d.nrows < 0xffffffffll && d.ld_bytes < 0xffffffffll;
         key_of[t] = vec ? d.bits * 256 + lpr : 0;
     }
-    open_side_streams(s);
-    const bool nt = (flags & ET_FLAG_NONTEMPORAL) != 0;
+    *work = true;
+    return ET_OK;
+}
+
+// Group the tables by key and call launch(key, pack, n) once per group.
+template <typename Launch>
+int quant_for_groups(const et_quant_desc* descs, int ntables,
+                     const int (&key_of)[ET_MAX_TABLES_PER_LAUNCH], Launch launch) {
     bool done[ET_MAX_TABLES_PER_LAUNCH] = {false};
     for (int t0 = 0; t0 < ntables; ++t0) {
         if (done[t0] || key_of[t0] < 0) continue;
@@ -513,20 +534,29 @@ inline int quant_dispatch(int out, const et_quant_desc* descs, int ntables, int6
             pack.d[n++] = descs[t];
             done[t] = true;
         }
-        const int key = key_of[t0];
-        int rc;
-        if (key == 0) {
-            rc = out == ET_F32   ? launch_quant_generic<float>(pack, n, batch, dst, ld_dst, nt, s)
-                 : out == ET_F16 ? launch_quant_generic<_Float16>(pack, n, batch, dst, ld_dst, nt, s)
-                                 : launch_quant_generic<__bf16>(pack, n, batch, dst, ld_dst, nt, s);
-        } else if (key / 256 == 8) {
-            rc = launch_quant_vec_bits<8>(key % 256, pack, n, batch, dst, ld_dst, out, nt, s);
-        } else {
-            rc = launch_quant_vec_bits<4>(key % 256, pack, n, batch, dst, ld_dst, out, nt, s);
-        }
+        const int rc = launch(key_of[t0], pack, n);
         if (rc != ET_OK) return rc;
     }
     return ET_OK;
+}
+
+inline int quant_dispatch(int out, const et_quant_desc* descs, int ntables, int64_t batch,
+                          void* dst, int64_t ld_dst, uint32_t flags, hipStream_t s) {
+    int key_of[ET_MAX_TABLES_PER_LAUNCH];
+    bool work;
+    const int rc = quant_validate(out, descs, ntables, batch, dst, ld_dst, flags, 0, key_of, &work);
+    if (rc != ET_OK || !work) return rc;
+    open_side_streams(s);
+    const bool nt = (flags & ET_FLAG_NONTEMPORAL) != 0;
+    return quant_for_groups(descs, ntables, key_of, [&](int key, const QuantPack& pack, int n) {
+        if (key == 0)
+            return out == ET_F32   ? launch_quant_generic<float>(pack, n, batch, dst, ld_dst, nt, s)
+                   : out == ET_F16 ? launch_quant_generic<_Float16>(pack, n, batch, dst, ld_dst, nt, s)
+                                   : launch_quant_generic<__bf16>(pack, n, batch, dst, ld_dst, nt, s);
+        if (key / 256 == 8)
+            return launch_quant_vec_bits<8>(key % 256, pack, n, batch, dst, ld_dst, out, nt, s);
+        return launch_quant_vec_bits<4>(key % 256, pack, n, batch, dst, ld_dst, out, nt, s);
+    });
 }
 
 }  // namespace et

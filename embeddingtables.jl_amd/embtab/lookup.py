@@ -153,8 +153,8 @@ def lookup_(dst: torch.Tensor, A: AbstractEmbeddingTable, I: torch.Tensor,
         descs = (_lib.WeightedDesc * 1)(weighted_desc(A, I, 0))
         weighted_launch(descs, 1, B, dst, _ld(dst), flags)
         return dst
-    if isinstance(A, QuantizedEmbedding):  # one et_quant_maplookup_prealloc launch
-        quant_launch(quant_descs([A], [I], B, 0), 1, B, dst, _ld(dst), flags)
+    if isinstance(A, QuantizedEmbedding):  # one et_quant / et_fp8_maplookup_prealloc launch
+        quant_launch(quant_descs([A], [I], B, 0), B, dst, _ld(dst), flags)
         return dst
     table, cpp = A.device_table()
     if isinstance(I, RaggedIndices):
@@ -397,7 +397,7 @@ class PreallocationPlan:
         self._quant = is_quantized_list(tables)  # all quantised, or none (a mix raises)
         if self._quant and wpos:
             raise ArgumentError("quantised tables beside weighted indices in one maplookup")
-        if self._quant:  # fixed-pool and ragged indices alike: et_quant_maplookup_prealloc
+        if self._quant:  # fixed-pool and ragged indices alike, one launch per format present
             if f16_fp32_acc:
                 raise ArgumentError("f16_fp32_acc belongs to Float16 tables: a quantised lookup "
                                     "always sums in Float32")
@@ -438,7 +438,7 @@ class PreallocationPlan:
             if self._n == 0:
                 return dst
         if self._quant:
-            quant_launch(self._descs, self._n, self._B, dst, self._ld, self._flags)
+            quant_launch(self._descs, self._B, dst, self._ld, self._flags)
             return dst
         stream = _lib.stream_handle(dst.device)
         if self._ragged:

@@ -1,10 +1,11 @@
-"""Row-wise quantised tables: INT8 / INT4 rows with a Float16 scale and bias per row,
-dequantised inside the pooled sum (include/embtab.h, "Row-wise quantised tables"; the layout
-of FBGEMM's Fused8BitRowwise / FusedNBitRowwise with half-precision headers).
+"""Row-wise quantised tables: INT8 / INT4 rows, or FP8 rows (OCP E4M3FN / E5M2), with a
+Float16 scale and bias per row, dequantised inside the pooled sum (include/embtab.h, "Row-wise
+quantised tables" and "FP8 rows"; the layout of FBGEMM's Fused8BitRowwise / FusedNBitRowwise
+with half-precision headers).
 
 A ``QuantizedEmbedding`` is an inference-only table: ``lookup`` / ``maplookup`` and
-``PreallocationPlan`` accept it under every strategy (one et_quant_maplookup_prealloc launch
-per call), ``rrule``, ``update_``, ``PhasedUpdate`` and the sharding classes refuse it.
+``PreallocationPlan`` accept it under every strategy (one et_quant_maplookup_prealloc or
+et_fp8_maplookup_prealloc launch per format in the call), ``rrule``, ``update_``, ``PhasedUpdate`` and the sharding classes refuse it.
 """
 from __future__ import annotations
 
@@ -17,6 +18,15 @@ from .ragged import RaggedIndices
 from .tables import AbstractEmbeddingTable, ArgumentError, Dynamic
 
 OUT_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
+# format name -> (ET_FP8_* of include/embtab.h or 0 for the integer formats, torch's view type)
+FORMATS = {"int": (0, None), "e4m3": (1, torch.float8_e4m3fn), "e5m2": (2, torch.float8_e5m2)}
+
+
+def check_format(format, bits) -> None:
+    if format not in FORMATS:
+        raise ArgumentError(f"format must be 'int', 'e4m3' or 'e5m2', got {format!r}")
+    if format != "int" and bits != 8:
+        raise ArgumentError(f"an FP8 table ({format}) has bits == 8, got {bits!r}")
 
 
 def payload_bytes(dim: int, bits: int) -> int:
@@ -30,7 +40,9 @@ def default_ld_bytes(dim: int, bits: int, split_header: bool = False) -> int:
 
 
 class QuantizedEmbedding(AbstractEmbeddingTable):
-    """``QuantizedEmbedding(packed, dim, bits, header=None)`` wraps an existing packed table.
+    """``QuantizedEmbedding(packed, dim, bits, header=None, format="int")`` wraps an existing
+    packed table.  ``format`` is ``"int"`` (unsigned levels, 8 or 4 bits) or ``"e4m3"`` /
+    ``"e5m2"`` (one OCP FP8 code per feature, ``bits == 8``).
 
     ``packed`` is a ``(R, ld_bytes)`` uint8 tensor with unit byte stride: row ``r`` holds the
     ``dim * bits / 8`` payload bytes first and, when ``header`` is None, the Float16 scale
@@ -40,13 +52,15 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
 
     lookup_type = Dynamic
 
-    def __init__(self, packed: torch.Tensor, dim: int, bits: int, header: torch.Tensor | None = None):
+    def __init__(self, packed: torch.Tensor, dim: int, bits: int,
+                 header: torch.Tensor | None = None, format: str = "int"):
         if not isinstance(packed, torch.Tensor) or packed.dim() != 2 or packed.dtype != torch.uint8:
             raise ArgumentError("QuantizedEmbedding expects a 2-D (R, ld_bytes) uint8 tensor")
         if isinstance(dim, bool) or not isinstance(dim, int) or dim < 1:
             raise ArgumentError(f"dim must be a positive int, got {dim!r}")
         if bits not in (8, 4):
             raise ArgumentError(f"bits must be 8 or 4, got {bits!r}")
+        check_format(format, bits)
         if bits == 4 and dim % 2:
             raise ArgumentError(f"4-bit rows need an even dim, got {dim}")
         if packed.shape[0] < 1:
@@ -73,18 +87,21 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
         self.header = header
         self.dim = dim
         self.bits = bits
+        self.format = format
         self.ld_bytes = ld
 
     def __repr__(self):
-        return (f"{self.dim}x{self.packed.shape[0]} QuantizedEmbedding{{INT{self.bits}, "
+        kind = f"INT{self.bits}" if self.format == "int" else f"FP8 {self.format.upper()}"
+        return (f"{self.dim}x{self.packed.shape[0]} QuantizedEmbedding{{{kind}, "
                 f"{'split' if self.header is not None else 'fused'} header, ld {self.ld_bytes}}}")
 
     @classmethod
     def quantize(cls, src, bits: int = 8, ld_bytes: int | None = None,
-                 split_header: bool = False) -> "QuantizedEmbedding":
-        """Quantise a Float32 ``(R, D)`` tensor or float table on the device
-        (et_quantize_rows: include/embtab.h's quantiser).  ``ld_bytes`` defaults to the payload
+                 split_header: bool = False, format: str = "int") -> "QuantizedEmbedding":
+        """Quantise a Float32 ``(R, D)`` tensor or float table on the device (et_quantize_rows,
+        or et_fp8_quantize_rows for ``format="e4m3"`` / ``"e5m2"``: include/embtab.h's quantisers).  ``ld_bytes`` defaults to the payload
         (+ 4 when fused) rounded up to 16; padding bytes are zero."""
+        check_format(format, bits)
         if isinstance(src, AbstractEmbeddingTable):
             if isinstance(src, QuantizedEmbedding):
                 raise TypeError("QuantizedEmbedding.quantize: the source is already quantised")
@@ -109,10 +126,15 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
         packed = torch.zeros((R, ld), dtype=torch.uint8, device=src.device)
         header = torch.zeros((R, 4), dtype=torch.uint8, device=src.device) if split_header else None
         ld_src = int(src.stride(0)) if R > 1 else D
-        _lib.check(_lib.load().et_quantize_rows(
-            src.data_ptr(), ld_src, R, D, bits, packed.data_ptr(), ld,
-            header.data_ptr() if header is not None else None, _lib.stream_handle(src.device)))
-        return cls(packed, D, bits, header)
+        hdr = header.data_ptr() if header is not None else None
+        L, stream = _lib.load(), _lib.stream_handle(src.device)
+        if format == "int":
+            _lib.check(L.et_quantize_rows(src.data_ptr(), ld_src, R, D, bits, packed.data_ptr(),
+                                          ld, hdr, stream))
+        else:
+            _lib.check(L.et_fp8_quantize_rows(FORMATS[format][0], src.data_ptr(), ld_src, R, D,
+                                              packed.data_ptr(), ld, hdr, stream))
+        return cls(packed, D, bits, header, format)
 
     # --- the table contract -------------------------------------------------------------
     def size(self):
@@ -152,14 +174,16 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
         """The ``(R, D)`` Float32 table ``q * scale + bias`` (one rounding per element)."""
         p = payload_bytes(self.dim, self.bits)
         raw = self.packed[:, :p]
-        if self.bits == 8:
+        if self.format != "int":  # the codes' exact Float32 values
+            q = raw.contiguous().view(FORMATS[self.format][1]).to(torch.float32)
+        elif self.bits == 8:
             q = raw.to(torch.float32)
         else:
             q = torch.stack((raw & 15, raw >> 4), dim=2).reshape(raw.shape[0], self.dim)
             q = q.to(torch.float32)
         h = self._headers().to(torch.float32)
-        # the product is exact in Float32 (8 x 11 significant bits), so addcmul's fused or
-        # unfused evaluation both round once
+        # the product is exact in Float32 (at most 8 x 11 significant bits), so addcmul's fused
+        # or unfused evaluation both round once
         return torch.addcmul(h[:, 1:2].expand_as(q), q, h[:, 0:1].expand_as(q))
 
     def _col(self, j: int) -> torch.Tensor:
@@ -195,7 +219,8 @@ def is_quantized_list(tables) -> bool:
 
 
 def quant_descs(tables, Is, B: int, k: int):
-    """et_quant_desc array of a list of quantised tables (fixed-pool and ragged indices)."""
+    """The et_quant_desc arrays of a list of quantised tables (fixed-pool and ragged indices),
+    one per format present: what `quant_launch` takes."""
     from .lookup import _check_idx, _ld, _trailing_size
 
     descs = (_lib.QuantDesc * len(tables))()
@@ -216,17 +241,41 @@ def quant_descs(tables, Is, B: int, k: int):
             descs[t] = _lib.QuantDesc(A.packed.data_ptr(), A.ld_bytes, R, D, A.bits, hdr, pool, 0,
                                       i.data_ptr(), 1 if i.dim() == 1 else _ld(i), None, 0, off)
         off += D
-    return descs
+    return quant_groups(tables, descs)
 
 
-def quant_launch(descs, n: int, B: int, dst: torch.Tensor, ld_dst: int, flags: int) -> None:
-    """et_quant_maplookup_prealloc over `n` descriptors, at most ET_MAX_TABLES_PER_LAUNCH a call."""
+def quant_groups(tables, descs):
+    """[(ET_FP8_* or 0, descriptor array)]: the descriptors of each format present, in list
+    order (every descriptor carries its own dst_row_off, so the split changes no result)."""
+    fmts = [FORMATS[A.format][0] for A in tables]
+    out = []
+    for fmt in sorted(set(fmts)):
+        pick = [t for t, f in enumerate(fmts) if f == fmt]
+        if len(pick) == len(fmts):
+            return [(fmt, descs)]
+        part = (_lib.QuantDesc * len(pick))()
+        for k, t in enumerate(pick):
+            part[k] = descs[t]
+        out.append((fmt, part))
+    return out
+
+
+def quant_launch(groups, B: int, dst: torch.Tensor, ld_dst: int, flags: int) -> None:
+    """et_quant_maplookup_prealloc / et_fp8_maplookup_prealloc over the descriptor groups of
+    `quant_groups`, at most ET_MAX_TABLES_PER_LAUNCH a call."""
     if dst.dtype not in OUT_DTYPES:
         raise ArgumentError(f"a quantised lookup writes Float32, Float16 or BFloat16, not {dst.dtype}")
     L = _lib.load()
     step = _lib.ET_MAX_TABLES_PER_LAUNCH
     size = ctypes.sizeof(_lib.QuantDesc)
-    for c in range(0, n, step):
-        _lib.check(L.et_quant_maplookup_prealloc(
-            _lib.et_dtype(dst), ctypes.addressof(descs) + c * size, min(step, n - c), B,
-            dst.data_ptr(), ld_dst, flags, _lib.stream_handle(dst.device)))
+    dt, stream = _lib.et_dtype(dst), _lib.stream_handle(dst.device)
+    for fmt, descs in groups:
+        n = len(descs)
+        for c in range(0, n, step):
+            part, m = ctypes.addressof(descs) + c * size, min(step, n - c)
+            if fmt == 0:
+                _lib.check(L.et_quant_maplookup_prealloc(dt, part, m, B, dst.data_ptr(), ld_dst,
+                                                         flags, stream))
+            else:
+                _lib.check(L.et_fp8_maplookup_prealloc(dt, fmt, part, m, B, dst.data_ptr(),
+                                                       ld_dst, flags, stream))

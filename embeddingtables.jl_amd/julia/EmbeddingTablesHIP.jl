@@ -657,7 +657,8 @@ end
 
 #####
 ##### Row-wise quantised tables (inference only; include/embtab.h "Row-wise quantised tables"):
-##### INT8 / INT4 rows with a Float16 scale and bias per row, dequantised inside the pooled sum.
+##### INT8 / INT4 rows, or FP8 rows (format 1 = OCP E4M3FN, 2 = OCP E5M2; 0 = the integer formats),
+##### with a Float16 scale and bias per row, dequantised inside the pooled sum.
 ##### `packed` is ld_bytes x R (column r = row r of the format: payload, then the fused header);
 ##### `header` is a 4 x R UInt8 array for the split form.  No counterpart in the reference.
 #####
@@ -683,24 +684,37 @@ struct QuantizedEmbedding
     dim::Int
     bits::Int
     header::Union{Nothing,HipMatrix{UInt8}}
+    format::Int
 end
+QuantizedEmbedding(packed, dim, bits, header) = QuantizedEmbedding(packed, dim, bits, header, 0)
+const FP8_FORMATS = (int = 0, e4m3 = 1, e5m2 = 2)
 EmbeddingTables.featuresize(Q::QuantizedEmbedding) = Q.dim
 Base.size(Q::QuantizedEmbedding) = (Q.dim, size(Q.packed, 2))
 
-# Quantise a dense Float32 D x R device matrix (et_quantize_rows); ld_bytes defaults to the
-# payload (+ 4 when fused) rounded up to 16.
+# Quantise a dense Float32 D x R device matrix (et_quantize_rows, or et_fp8_quantize_rows for
+# format = :e4m3 / :e5m2, which need bits = 8); ld_bytes defaults to the payload (+ 4 when fused)
+# rounded up to 16.
 function QuantizedEmbedding(src::HipMatrix{Float32}; bits::Integer = 8, split_header::Bool = false,
+                            format::Symbol = :int,
                             ld_bytes::Integer = cld(size(src, 1) * bits ÷ 8 +
                                                     (split_header ? 0 : 4), 16) * 16)
     D, R = size(src)
     packed = HipArray{UInt8}(undef, ld_bytes, R)
     ccall((:hipMemset, libhip), Cint, (Ptr{Cvoid}, Cint, Csize_t), packed.ptr, 0, ld_bytes * R)
     header = split_header ? HipArray{UInt8}(undef, 4, R) : nothing
-    check(ccall((:et_quantize_rows, libembtab), Cint,
-                (Ptr{Float32}, Int64, Int64, Int32, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
-                src.ptr, leading(src), R, D, bits, packed.ptr, ld_bytes,
-                header === nothing ? C_NULL : header.ptr, stream()))
-    return QuantizedEmbedding(packed, D, bits, header)
+    fmt = FP8_FORMATS[format]
+    fmt == 0 || bits == 8 || throw(ArgumentError("an FP8 table has bits == 8"))
+    hdr = header === nothing ? C_NULL : header.ptr
+    if fmt == 0
+        check(ccall((:et_quantize_rows, libembtab), Cint,
+                    (Ptr{Float32}, Int64, Int64, Int32, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                    src.ptr, leading(src), R, D, bits, packed.ptr, ld_bytes, hdr, stream()))
+    else
+        check(ccall((:et_fp8_quantize_rows, libembtab), Cint,
+                    (Cint, Ptr{Float32}, Int64, Int64, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                    fmt, src.ptr, leading(src), R, D, packed.ptr, ld_bytes, hdr, stream()))
+    end
+    return QuantizedEmbedding(packed, D, bits, header, fmt)
 end
 
 _quant_hdr(Q::QuantizedEmbedding) = Q.header === nothing ? Ptr{Cvoid}(C_NULL) : Ptr{Cvoid}(Q.header.ptr)
@@ -717,22 +731,32 @@ _quant_batch(I::HipArray) = size(I, ndims(I))
 _quant_batch(R::RaggedIndices) = batchsize(R)
 
 # dst: Float32, or Float16 (the Float32 sums rounded once)
-function _quant_maplookup(::Type{U}, descs::Vector{QuantDesc}, batch, p, ld) where {U}
-    for c in 1:ET_MAX_TABLES_PER_LAUNCH:length(descs)
-        part = descs[c:min(c + ET_MAX_TABLES_PER_LAUNCH - 1, length(descs))]
-        check(ccall((:et_quant_maplookup_prealloc, libembtab), Cint,
-                    (Cint, Ptr{QuantDesc}, Int32, Int64, Ptr{Cvoid}, Int64, UInt32, Ptr{Cvoid}),
-                    et_dtype(U), part, length(part), batch, p, ld, ET_FLAG_NONTEMPORAL, stream()))
+# one call per format present (and per 32 tables): every descriptor carries its dst_row_off
+function _quant_maplookup(::Type{U}, descs::Vector{QuantDesc}, formats, batch, p, ld) where {U}
+    for fmt in sort(unique(formats))
+        mine = descs[findall(==(fmt), formats)]
+        for c in 1:ET_MAX_TABLES_PER_LAUNCH:length(mine)
+            part = mine[c:min(c + ET_MAX_TABLES_PER_LAUNCH - 1, length(mine))]
+            if fmt == 0
+                check(ccall((:et_quant_maplookup_prealloc, libembtab), Cint,
+                            (Cint, Ptr{QuantDesc}, Int32, Int64, Ptr{Cvoid}, Int64, UInt32, Ptr{Cvoid}),
+                            et_dtype(U), part, length(part), batch, p, ld, ET_FLAG_NONTEMPORAL, stream()))
+            else
+                check(ccall((:et_fp8_maplookup_prealloc, libembtab), Cint,
+                            (Cint, Cint, Ptr{QuantDesc}, Int32, Int64, Ptr{Cvoid}, Int64, UInt32, Ptr{Cvoid}),
+                            et_dtype(U), fmt, part, length(part), batch, p, ld, ET_FLAG_NONTEMPORAL, stream()))
+            end
+        end
     end
 end
 
 function lookup!(dst, Q::QuantizedEmbedding, I::Union{HipVector{Int},HipMatrix{Int},RaggedIndices})
     p, ld = _ptr_ld(dst)
-    _quant_maplookup(eltype(dst), [_quant_desc(Q, I, 0)], _quant_batch(I), p, ld)
+    _quant_maplookup(eltype(dst), [_quant_desc(Q, I, 0)], [Q.format], _quant_batch(I), p, ld)
     return dst
 end
 
-# a list of only quantised tables: ONE fused launch (per 32 tables)
+# a list of only quantised tables: ONE fused launch per format present (and per 32 tables)
 function maplookup!(strategy::PreallocationStrategy, dst::HipMatrix{U},
                     x::Vector{QuantizedEmbedding}, I::Vector; kw...) where {U}
     descs = Vector{QuantDesc}(undef, length(x))
@@ -741,7 +765,7 @@ function maplookup!(strategy::PreallocationStrategy, dst::HipMatrix{U},
         descs[t] = _quant_desc(Q, i, off)
         off += Q.dim
     end
-    _quant_maplookup(U, descs, _quant_batch(first(I)), dst.ptr, leading(dst))
+    _quant_maplookup(U, descs, [Q.format for Q in x], _quant_batch(first(I)), dst.ptr, leading(dst))
     return dst
 end
 

@@ -782,6 +782,62 @@ int et_quant_maplookup_prealloc(int dst_dtype, const et_quant_desc* descs, int32
                                 int64_t batch, void* dst, int64_t ld_dst, uint32_t flags,
                                 void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * FP8 rows (inference only): the row layout above, unchanged, with one OCP FP8 code per
+ * feature in the payload.  Row r starts at table + (r-1)*ld_bytes; the payload is `dim` bytes
+ * (et_quant_desc.bits is 8); the header is the Float16 scale then the Float16 bias, fused behind
+ * the payload or in a split `hdr` array; the ld_bytes rules are those above and no result
+ * depends on padding.  One format per call:
+ *   ET_FP8_E4M3  OCP E4M3FN: exponent bias 7, no infinities, NaN is S.1111.111, largest value
+ *                448.
+ *   ET_FP8_E5M2  OCP E5M2: IEEE-like, exponent bias 15, largest finite value 57344.
+ *
+ * Dequantisation, in Float32:  v_f = float(q_f)*float(scale) + float(bias).
+ * An FP8 value has at most 4 significant bits and a half has 11, so the product has at most 15,
+ * and its exponent stays inside Float32's range (from 2^-40 up to about 3.8e9): the product is
+ * EXACT, and v_f carries exactly one rounding whether the expression is evaluated as a multiply
+ * and an add or as one fused multiply-add — the argument of the integer formats.
+ *
+ * NaN and Inf codes in a table from another producer follow IEEE arithmetic; the sign and
+ * payload of a resulting NaN are unspecified.  An index outside 1..nrows adds +0 to every
+ * feature whatever row 1 holds (a NaN code times a zero scale would be NaN: the row's value is
+ * replaced, not only its header).
+ *
+ * Quantiser, per row; every operation is one correctly rounded Float32 operation; FMAX is 448
+ * (E4M3) or 57344 (E5M2):
+ *   lo = min_f x_f;  hi = max_f x_f
+ *   bias  = half_rne((lo + hi) / 2);  b = float(bias)
+ *   amax  = max(hi - b, b - lo)
+ *   scale = half_rne(amax / FMAX);  if float(scale) is not a finite value > 0: scale = 1.0
+ *   s = float(scale);  q_f = fp8_rne(min(max((x_f - b) / s, -FMAX), FMAX))
+ * The clamp comes first, then one rounding to the format (ties to even), so no NaN or Inf code
+ * is ever produced; the sign of a zero quotient is kept.  The bias centres the row: FP8's
+ * precision sits around zero, and a row with an offset would otherwise lose everything.  A row
+ * holding a non-finite value or |x| > 65504 gets unspecified contents (never a fault).  The
+ * quantiser writes the payload and the header only, never the padding.
+ * ------------------------------------------------------------------------------- */
+#define ET_FP8_E4M3 1
+#define ET_FP8_E5M2 2
+
+/* et_quantize_rows for an FP8 table (bits is 8).  A format that is neither of the two:
+ * ET_ERR_UNSUPPORTED; every other rule is et_quantize_rows'. */
+int et_fp8_quantize_rows(int format, const float* src, int64_t ld_src, int64_t nrows, int32_t dim,
+                         void* table, int64_t ld_bytes, void* hdr, void* stream);
+
+/* et_quant_maplookup_prealloc over FP8 tables of one format: the same pooled sum (a COPY of the
+ * first row's v, the others added one at a time in index order in Float32, +0 for an empty bag,
+ * one RNE conversion to ET_F32 / ET_F16 / ET_BF16), the same descriptors, flags, destination
+ * types, out-of-range counting and argument rules, all checked before any device work.  The
+ * ET_F32 result equals et_maplookup_prealloc / et_ragged_maplookup_prealloc on the dequantised
+ * Float32 table bit for bit.  descs[t].bits != 8: ET_ERR_ARG; a format that is neither of the
+ * two: ET_ERR_UNSUPPORTED.  Fixed-pool and ragged tables, fused and split headers may share a
+ * call; rows that are whole 16-byte vectors (the rule above) take the vector kernel, every
+ * other shape a generic one with the same results.  Stream-ordered on the caller's stream
+ * only, allocates nothing, never synchronises: capturable. */
+int et_fp8_maplookup_prealloc(int dst_dtype, int format, const et_quant_desc* descs, int32_t ntables,
+                              int64_t batch, void* dst, int64_t ld_dst, uint32_t flags,
+                              void* stream);
+
 /* Assemble the Preallocation concat from per-rank slabs after an all-gather
  * (table-wise sharding across GPUs, no counterpart in the single-process
  * reference): slab r is a (slab_ld x batch) column-major block at
