@@ -1717,6 +1717,9 @@ ET_OOB_READER(lookup)
 // FP8 rows (et_fp8_quantize_rows, et_fp8_maplookup_prealloc).
 #include "et_fp8.hip"
 
+// MXFP4 rows (et_mx4_quantize_rows, et_mx4_maplookup_prealloc).
+#include "et_mx4.hip"
+
 #ifdef ET_WG_TIMELINE
 // Profiling build only: copies the striped launch's workgroup records (2 x uint4 each)
 // to host memory; returns the number copied.

@@ -382,8 +382,10 @@ __global__ __launch_bounds__(256) void k_quantize_rows(const float* __restrict__
 // ---------------------------------------------------------------------------
 
 // ET_ERR_ARG unless (dim, bits, ld_bytes) describe a row of the format; *payload = its bytes.
+// `trailer`: the bytes a fused row carries behind its payload (the 4-byte header; MXFP4: its
+// scale bytes).
 inline int quant_row_check(const char* what, int t, int32_t dim, int32_t bits, int64_t ld_bytes,
-                           bool fused, int64_t* payload) {
+                           bool fused, int64_t* payload, int64_t trailer = 4) {
     if (bits != 8 && bits != 4) return fail(ET_ERR_ARG, "%s %d: bits %d is not 8 or 4", what, t, bits);
     if (dim < 0) return fail(ET_ERR_ARG, "%s %d: negative dim", what, t);
     if (bits == 4 && (dim & 1)) return fail(ET_ERR_ARG, "%s %d: odd dim %d with 4 bits", what, t, dim);
@@ -391,9 +393,9 @@ inline int quant_row_check(const char* what, int t, int32_t dim, int32_t bits, i
     if (ld_bytes < 0 || ld_bytes % 4 != 0)
         return fail(ET_ERR_ARG, "%s %d: ld_bytes %lld is not a non-negative multiple of 4", what, t,
                     (long long)ld_bytes);
-    if (ld_bytes < *payload + (fused ? 4 : 0))
+    if (ld_bytes < *payload + (fused ? trailer : 0))
         return fail(ET_ERR_ARG, "%s %d: ld_bytes %lld < %lld (payload%s)", what, t,
-                    (long long)ld_bytes, (long long)(*payload + (fused ? 4 : 0)),
+                    (long long)ld_bytes, (long long)(*payload + (fused ? trailer : 0)),
                     fused ? " + fused header" : "");
     return ET_OK;
 }
@@ -470,10 +472,11 @@ int launch_quant_generic(const QuantPack& pack, int n, int64_t batch, void* dst,
 
 // Validate (everything before any device work) and key every table by its kernel: -1 nothing
 // to do, 0 = generic, else bits * 256 + lane-group capacity.  `only_bits` != 0 (the FP8 entry)
-// refuses every other width.  *work = false: the call is a no-op.
+// refuses every other width.  `mx4` (the MXFP4 entry): dim is a multiple of 32 and a fused row
+// ends in dim / 32 scale bytes instead of the header.  *work = false: the call is a no-op.
 inline int quant_validate(int out, const et_quant_desc* descs, int ntables, int64_t batch,
                           const void* dst, int64_t ld_dst, uint32_t flags, int only_bits,
-                          int (&key_of)[ET_MAX_TABLES_PER_LAUNCH], bool* work) {
+                          int (&key_of)[ET_MAX_TABLES_PER_LAUNCH], bool* work, bool mx4 = false) {
     *work = false;
     if (out != ET_F32 && out != ET_F16 && out != ET_BF16)
         return fail(ET_ERR_UNSUPPORTED, "destination dtype %d (Float32, Float16 or BFloat16)", out);
@@ -490,9 +493,12 @@ inline int quant_validate(int out, const et_quant_desc* descs, int ntables, int6
         const et_quant_desc& d = descs[t];
         if (only_bits && d.bits != only_bits)
             return fail(ET_ERR_ARG, "table %d: bits %d, this entry takes %d", t, d.bits, only_bits);
+        if (mx4 && d.dim % 32 != 0)
+            return fail(ET_ERR_ARG, "table %d: dim %d is not a multiple of 32 (one MXFP4 block)", t,
+                        d.dim);
         int64_t payload = 0;
         const int rc = quant_row_check("table", t, d.dim, d.bits, d.ld_bytes, d.hdr == nullptr,
-                                       &payload);
+                                       &payload, mx4 ? d.dim / 32 : 4);
         if (rc != ET_OK) return rc;
         const bool ragged = d.colptr != nullptr;
         if (d.nrows < 0 || (ragged ? d.nnz < 0 : d.pool < 0 || d.ld_idx < 0))

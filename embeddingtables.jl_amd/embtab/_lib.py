@@ -84,6 +84,8 @@ EXPORTS = (
     "et_quant_maplookup_prealloc",
     "et_fp8_quantize_rows",
     "et_fp8_maplookup_prealloc",
+    "et_mx4_quantize_rows",
+    "et_mx4_maplookup_prealloc",
     "et_concat_slabs",
     "et_split_slabs",
     "et_push_cols",
@@ -336,6 +338,8 @@ def load() -> ctypes.CDLL:
         "et_quant_maplookup_prealloc": ([c_int, vp, i32, i64, vp, i64, u32, vp], c_int),
         "et_fp8_quantize_rows": ([c_int, vp, i64, i64, i32, vp, i64, vp, vp], c_int),
         "et_fp8_maplookup_prealloc": ([c_int, c_int, vp, i32, i64, vp, i64, u32, vp], c_int),
+        "et_mx4_quantize_rows": ([vp, i64, i64, i32, vp, i64, vp, vp], c_int),
+        "et_mx4_maplookup_prealloc": ([c_int, vp, i32, i64, vp, i64, u32, vp], c_int),
         "et_concat_slabs": ([c_int, vp, i32, i64, i64, vp, vp, vp, i64, vp], c_int),
         "et_split_slabs": ([c_int, vp, i64, i64, i32, vp, vp, vp, i64, vp], c_int),
         "et_push_cols": ([c_int, vp, i64, i64, i64, i64, vp, i32, vp], c_int),

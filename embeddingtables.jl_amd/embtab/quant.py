@@ -1,11 +1,13 @@
 """Row-wise quantised tables: INT8 / INT4 rows, or FP8 rows (OCP E4M3FN / E5M2), with a
 Float16 scale and bias per row, dequantised inside the pooled sum (include/embtab.h, "Row-wise
 quantised tables" and "FP8 rows"; the layout of FBGEMM's Fused8BitRowwise / FusedNBitRowwise
-with half-precision headers).
+with half-precision headers); or MXFP4 rows (OCP Microscaling FP4: blocks of 32 E2M1 codes under
+one E8M0 scale byte, no header and no bias; include/embtab.h, "MXFP4 rows").
 
 A ``QuantizedEmbedding`` is an inference-only table: ``lookup`` / ``maplookup`` and
-``PreallocationPlan`` accept it under every strategy (one et_quant_maplookup_prealloc or
-et_fp8_maplookup_prealloc launch per format in the call), ``rrule``, ``update_``, ``PhasedUpdate`` and the sharding classes refuse it.
+``PreallocationPlan`` accept it under every strategy (one et_quant_maplookup_prealloc,
+et_fp8_maplookup_prealloc or et_mx4_maplookup_prealloc launch per format in the call),
+``rrule``, ``update_``, ``PhasedUpdate`` and the sharding classes refuse it.
 """
 from __future__ import annotations
 
@@ -18,31 +20,55 @@ from .ragged import RaggedIndices
 from .tables import AbstractEmbeddingTable, ArgumentError, Dynamic
 
 OUT_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
-# format name -> (ET_FP8_* of include/embtab.h or 0 for the integer formats, torch's view type)
-FORMATS = {"int": (0, None), "e4m3": (1, torch.float8_e4m3fn), "e5m2": (2, torch.float8_e5m2)}
+# format name -> (launch group: ET_FP8_* of include/embtab.h, 0 for the integer formats, 3 for
+# MXFP4; torch's view type of an FP8 code)
+FORMATS = {"int": (0, None), "e4m3": (1, torch.float8_e4m3fn), "e5m2": (2, torch.float8_e5m2),
+           "mxfp4": (3, None)}
+E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # the magnitude codes; bit 3 is the sign
 
 
-def check_format(format, bits) -> None:
+def check_format(format, bits, dim=None) -> int:
+    """The `bits` of a table of `format` (None: the format's own, 4 for MXFP4 and 8 otherwise)."""
     if format not in FORMATS:
-        raise ArgumentError(f"format must be 'int', 'e4m3' or 'e5m2', got {format!r}")
-    if format != "int" and bits != 8:
+        raise ArgumentError(f"format must be 'int', 'e4m3', 'e5m2' or 'mxfp4', got {format!r}")
+    if bits is None:
+        bits = 4 if format == "mxfp4" else 8
+    if format in ("e4m3", "e5m2") and bits != 8:
         raise ArgumentError(f"an FP8 table ({format}) has bits == 8, got {bits!r}")
+    if format == "mxfp4":
+        if bits != 4:
+            raise ArgumentError(f"an MXFP4 table has bits == 4, got {bits!r}")
+        if dim is not None and dim % 32:
+            raise ArgumentError(f"MXFP4 rows are blocks of 32 features: dim {dim} is no multiple")
+    return bits
 
 
 def payload_bytes(dim: int, bits: int) -> int:
     return dim * bits // 8
 
 
-def default_ld_bytes(dim: int, bits: int, split_header: bool = False) -> int:
-    """Payload (+ 4 for a fused header) rounded up to 16 bytes."""
-    n = payload_bytes(dim, bits) + (0 if split_header else 4)
+def trailer_bytes(dim: int, format: str = "int") -> int:
+    """What a fused row carries behind its payload: the 4-byte header, or MXFP4's scale bytes."""
+    return dim // 32 if format == "mxfp4" else 4
+
+
+def split_width(dim: int, format: str = "int") -> int:
+    """Bytes per row of the split header array (MXFP4: the scale bytes rounded up to 4)."""
+    return (dim // 32 + 3) // 4 * 4 if format == "mxfp4" else 4
+
+
+def default_ld_bytes(dim: int, bits: int, split_header: bool = False, format: str = "int") -> int:
+    """Payload (+ the fused header or scale bytes) rounded up to 16 bytes."""
+    n = payload_bytes(dim, bits) + (0 if split_header else trailer_bytes(dim, format))
     return max((n + 15) // 16 * 16, 16)
 
 
 class QuantizedEmbedding(AbstractEmbeddingTable):
     """``QuantizedEmbedding(packed, dim, bits, header=None, format="int")`` wraps an existing
     packed table.  ``format`` is ``"int"`` (unsigned levels, 8 or 4 bits) or ``"e4m3"`` /
-    ``"e5m2"`` (one OCP FP8 code per feature, ``bits == 8``).
+    ``"e5m2"`` (one OCP FP8 code per feature, ``bits == 8``), or ``"mxfp4"`` (``bits == 4``,
+    ``dim % 32 == 0``: the rows end in ``dim / 32`` scale bytes instead of the header, and
+    ``header`` is the split scale array, ``(R, round_up(dim / 32, 4))`` uint8).
 
     ``packed`` is a ``(R, ld_bytes)`` uint8 tensor with unit byte stride: row ``r`` holds the
     ``dim * bits / 8`` payload bytes first and, when ``header`` is None, the Float16 scale
@@ -60,7 +86,7 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
             raise ArgumentError(f"dim must be a positive int, got {dim!r}")
         if bits not in (8, 4):
             raise ArgumentError(f"bits must be 8 or 4, got {bits!r}")
-        check_format(format, bits)
+        check_format(format, bits, dim)
         if bits == 4 and dim % 2:
             raise ArgumentError(f"4-bit rows need an even dim, got {dim}")
         if packed.shape[0] < 1:
@@ -68,7 +94,7 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
         if packed.shape[1] > 1 and packed.stride(1) != 1:
             raise ArgumentError("the bytes of a row must be contiguous (stride(1) == 1)")
         ld = int(packed.stride(0)) if packed.shape[0] > 1 else int(packed.shape[1])
-        need = payload_bytes(dim, bits) + (4 if header is None else 0)
+        need = payload_bytes(dim, bits) + (trailer_bytes(dim, format) if header is None else 0)
         if packed.shape[1] < need:
             raise ArgumentError(f"rows of {packed.shape[1]} bytes hold no {bits}-bit row of dim "
                                 f"{dim}{' with its fused header' if header is None else ''} "
@@ -76,7 +102,12 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
         if ld % 4 or ld < need:
             raise ArgumentError(f"ld_bytes {ld} must be a multiple of 4 and at least {need}")
         if header is not None:
-            if not isinstance(header, torch.Tensor) or header.dim() != 2 or \
+            if format == "mxfp4":
+                if not isinstance(header, torch.Tensor) or header.dim() != 2 or \
+                        (header.dtype, header.shape[1]) != (torch.uint8, split_width(dim, format)):
+                    raise ArgumentError(f"the split scales of an MXFP4 table of dim {dim} are a "
+                                        f"(R, {split_width(dim, format)}) uint8 tensor")
+            elif not isinstance(header, torch.Tensor) or header.dim() != 2 or \
                     (header.dtype, header.shape[1]) not in ((torch.uint8, 4), (torch.float16, 2)):
                 raise ArgumentError("header must be a (R, 4) uint8 or (R, 2) float16 tensor")
             if header.shape[0] != packed.shape[0] or not header.is_contiguous():
@@ -91,17 +122,20 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
         self.ld_bytes = ld
 
     def __repr__(self):
-        kind = f"INT{self.bits}" if self.format == "int" else f"FP8 {self.format.upper()}"
+        kind = f"INT{self.bits}" if self.format == "int" else \
+            "MXFP4" if self.format == "mxfp4" else f"FP8 {self.format.upper()}"
         return (f"{self.dim}x{self.packed.shape[0]} QuantizedEmbedding{{{kind}, "
                 f"{'split' if self.header is not None else 'fused'} header, ld {self.ld_bytes}}}")
 
     @classmethod
-    def quantize(cls, src, bits: int = 8, ld_bytes: int | None = None,
+    def quantize(cls, src, bits: int | None = None, ld_bytes: int | None = None,
                  split_header: bool = False, format: str = "int") -> "QuantizedEmbedding":
         """Quantise a Float32 ``(R, D)`` tensor or float table on the device (et_quantize_rows,
-        or et_fp8_quantize_rows for ``format="e4m3"`` / ``"e5m2"``: include/embtab.h's quantisers).  ``ld_bytes`` defaults to the payload
-        (+ 4 when fused) rounded up to 16; padding bytes are zero."""
-        check_format(format, bits)
+        et_fp8_quantize_rows for ``format="e4m3"`` / ``"e5m2"`` or et_mx4_quantize_rows for
+        ``"mxfp4"``: include/embtab.h's quantisers).  ``bits`` defaults to the format's own (4 for
+        MXFP4, 8 otherwise); ``ld_bytes`` to the payload (+ the header or scale bytes when fused)
+        rounded up to 16; padding bytes are zero."""
+        bits = check_format(format, bits)
         if isinstance(src, AbstractEmbeddingTable):
             if isinstance(src, QuantizedEmbedding):
                 raise TypeError("QuantizedEmbedding.quantize: the source is already quantised")
@@ -117,20 +151,25 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
             raise ArgumentError(f"bits must be 8 or 4, got {bits!r}")
         if R < 1 or D < 1 or (bits == 4 and D % 2):
             raise ArgumentError(f"cannot quantise a {R} x {D} table to {bits} bits")
+        check_format(format, bits, D)
         if D > 1 and src.stride(1) != 1:
             src = src.contiguous()
-        need = payload_bytes(D, bits) + (0 if split_header else 4)
-        ld = default_ld_bytes(D, bits, split_header) if ld_bytes is None else int(ld_bytes)
+        need = payload_bytes(D, bits) + (0 if split_header else trailer_bytes(D, format))
+        ld = default_ld_bytes(D, bits, split_header, format) if ld_bytes is None else int(ld_bytes)
         if ld % 4 or ld < need:
             raise ArgumentError(f"ld_bytes {ld} must be a multiple of 4 and at least {need}")
         packed = torch.zeros((R, ld), dtype=torch.uint8, device=src.device)
-        header = torch.zeros((R, 4), dtype=torch.uint8, device=src.device) if split_header else None
+        header = torch.zeros((R, split_width(D, format)), dtype=torch.uint8,
+                             device=src.device) if split_header else None
         ld_src = int(src.stride(0)) if R > 1 else D
         hdr = header.data_ptr() if header is not None else None
         L, stream = _lib.load(), _lib.stream_handle(src.device)
         if format == "int":
             _lib.check(L.et_quantize_rows(src.data_ptr(), ld_src, R, D, bits, packed.data_ptr(),
                                           ld, hdr, stream))
+        elif format == "mxfp4":
+            _lib.check(L.et_mx4_quantize_rows(src.data_ptr(), ld_src, R, D, packed.data_ptr(), ld,
+                                              hdr, stream))
         else:
             _lib.check(L.et_fp8_quantize_rows(FORMATS[format][0], src.data_ptr(), ld_src, R, D,
                                               packed.data_ptr(), ld, hdr, stream))
@@ -170,8 +209,25 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
         p = payload_bytes(self.dim, self.bits)
         return self.packed[:, p:p + 4].contiguous().view(torch.float16)
 
+    def _dequantize_mxfp4(self) -> torch.Tensor:
+        """E2M1(q) * 2^(e - 127), exact: the scale is assembled as Float64 bits (e - 127 + 1023
+        is a normal exponent for every e), the product is exact in Float64 and every
+        representable result converts to Float32 unchanged; e = 255 is NaN."""
+        p, nb = self.dim // 2, self.dim // 32
+        raw = self.packed[:, :p]
+        e = (self.header[:, :nb] if self.header is not None else self.packed[:, p:p + nb])
+        e = e.to(torch.int64)
+        q = torch.stack((raw & 15, raw >> 4), dim=2).reshape(raw.shape[0], self.dim).to(torch.int64)
+        lut = torch.tensor(E2M1 + tuple(-v for v in E2M1), dtype=torch.float64, device=raw.device)
+        scale = ((e + (1023 - 127)) << 52).view(torch.float64)
+        scale = torch.where(e == 255, torch.full_like(scale, float("nan")), scale)
+        return (lut[q] * scale.repeat_interleave(32, dim=1)).to(torch.float32)
+
     def dequantize(self) -> torch.Tensor:
-        """The ``(R, D)`` Float32 table ``q * scale + bias`` (one rounding per element)."""
+        """The ``(R, D)`` Float32 table ``q * scale + bias`` (one rounding per element); for
+        MXFP4 rows ``E2M1(q) * 2^(e - 127)`` (no rounding)."""
+        if self.format == "mxfp4":
+            return self._dequantize_mxfp4()
         p = payload_bytes(self.dim, self.bits)
         raw = self.packed[:, :p]
         if self.format != "int":  # the codes' exact Float32 values
@@ -245,8 +301,8 @@ def quant_descs(tables, Is, B: int, k: int):
 
 
 def quant_groups(tables, descs):
-    """[(ET_FP8_* or 0, descriptor array)]: the descriptors of each format present, in list
-    order (every descriptor carries its own dst_row_off, so the split changes no result)."""
+    """[(launch group of FORMATS, descriptor array)]: the descriptors of each format present, in
+    list order (every descriptor carries its own dst_row_off, so the split changes no result)."""
     fmts = [FORMATS[A.format][0] for A in tables]
     out = []
     for fmt in sorted(set(fmts)):
@@ -261,8 +317,8 @@ def quant_groups(tables, descs):
 
 
 def quant_launch(groups, B: int, dst: torch.Tensor, ld_dst: int, flags: int) -> None:
-    """et_quant_maplookup_prealloc / et_fp8_maplookup_prealloc over the descriptor groups of
-    `quant_groups`, at most ET_MAX_TABLES_PER_LAUNCH a call."""
+    """et_quant_maplookup_prealloc / et_fp8_maplookup_prealloc / et_mx4_maplookup_prealloc over
+    the descriptor groups of `quant_groups`, at most ET_MAX_TABLES_PER_LAUNCH a call."""
     if dst.dtype not in OUT_DTYPES:
         raise ArgumentError(f"a quantised lookup writes Float32, Float16 or BFloat16, not {dst.dtype}")
     L = _lib.load()
@@ -276,6 +332,9 @@ def quant_launch(groups, B: int, dst: torch.Tensor, ld_dst: int, flags: int) -> 
             if fmt == 0:
                 _lib.check(L.et_quant_maplookup_prealloc(dt, part, m, B, dst.data_ptr(), ld_dst,
                                                          flags, stream))
+            elif fmt == FORMATS["mxfp4"][0]:
+                _lib.check(L.et_mx4_maplookup_prealloc(dt, part, m, B, dst.data_ptr(), ld_dst,
+                                                       flags, stream))
             else:
                 _lib.check(L.et_fp8_maplookup_prealloc(dt, fmt, part, m, B, dst.data_ptr(),
                                                        ld_dst, flags, stream))

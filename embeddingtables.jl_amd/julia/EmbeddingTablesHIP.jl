@@ -658,7 +658,8 @@ end
 #####
 ##### Row-wise quantised tables (inference only; include/embtab.h "Row-wise quantised tables"):
 ##### INT8 / INT4 rows, or FP8 rows (format 1 = OCP E4M3FN, 2 = OCP E5M2; 0 = the integer formats),
-##### with a Float16 scale and bias per row, dequantised inside the pooled sum.
+##### with a Float16 scale and bias per row, dequantised inside the pooled sum; or MXFP4 rows
+##### (format 3: bits = 4, dim a multiple of 32, dim / 32 E8M0 scale bytes instead of the header).
 ##### `packed` is ld_bytes x R (column r = row r of the format: payload, then the fused header);
 ##### `header` is a 4 x R UInt8 array for the split form.  No counterpart in the reference.
 #####
@@ -687,25 +688,33 @@ struct QuantizedEmbedding
     format::Int
 end
 QuantizedEmbedding(packed, dim, bits, header) = QuantizedEmbedding(packed, dim, bits, header, 0)
-const FP8_FORMATS = (int = 0, e4m3 = 1, e5m2 = 2)
+const FP8_FORMATS = (int = 0, e4m3 = 1, e5m2 = 2, mxfp4 = 3)
 EmbeddingTables.featuresize(Q::QuantizedEmbedding) = Q.dim
 Base.size(Q::QuantizedEmbedding) = (Q.dim, size(Q.packed, 2))
 
-# Quantise a dense Float32 D x R device matrix (et_quantize_rows, or et_fp8_quantize_rows for
-# format = :e4m3 / :e5m2, which need bits = 8); ld_bytes defaults to the payload (+ 4 when fused)
-# rounded up to 16.
-function QuantizedEmbedding(src::HipMatrix{Float32}; bits::Integer = 8, split_header::Bool = false,
-                            format::Symbol = :int,
+# Quantise a dense Float32 D x R device matrix (et_quantize_rows, et_fp8_quantize_rows for
+# format = :e4m3 / :e5m2, which need bits = 8, or et_mx4_quantize_rows for format = :mxfp4, which
+# needs bits = 4 and D % 32 == 0); ld_bytes defaults to the payload (+ 4, or MXFP4's D / 32 scale
+# bytes, when fused) rounded up to 16.
+function QuantizedEmbedding(src::HipMatrix{Float32}; format::Symbol = :int,
+                            bits::Integer = format == :mxfp4 ? 4 : 8, split_header::Bool = false,
                             ld_bytes::Integer = cld(size(src, 1) * bits ÷ 8 +
-                                                    (split_header ? 0 : 4), 16) * 16)
+                                                    (split_header ? 0 : format == :mxfp4 ?
+                                                     size(src, 1) ÷ 32 : 4), 16) * 16)
     D, R = size(src)
     packed = HipArray{UInt8}(undef, ld_bytes, R)
     ccall((:hipMemset, libhip), Cint, (Ptr{Cvoid}, Cint, Csize_t), packed.ptr, 0, ld_bytes * R)
-    header = split_header ? HipArray{UInt8}(undef, 4, R) : nothing
     fmt = FP8_FORMATS[format]
-    fmt == 0 || bits == 8 || throw(ArgumentError("an FP8 table has bits == 8"))
+    header = split_header ? HipArray{UInt8}(undef, fmt == 3 ? cld(D ÷ 32, 4) * 4 : 4, R) : nothing
+    fmt == 0 || fmt == 3 || bits == 8 || throw(ArgumentError("an FP8 table has bits == 8"))
+    fmt != 3 || (bits == 4 && D % 32 == 0) ||
+        throw(ArgumentError("an MXFP4 table has bits == 4 and a dim that is a multiple of 32"))
     hdr = header === nothing ? C_NULL : header.ptr
-    if fmt == 0
+    if fmt == 3
+        check(ccall((:et_mx4_quantize_rows, libembtab), Cint,
+                    (Ptr{Float32}, Int64, Int64, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
+                    src.ptr, leading(src), R, D, packed.ptr, ld_bytes, hdr, stream()))
+    elseif fmt == 0
         check(ccall((:et_quantize_rows, libembtab), Cint,
                     (Ptr{Float32}, Int64, Int64, Int32, Int32, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}),
                     src.ptr, leading(src), R, D, bits, packed.ptr, ld_bytes, hdr, stream()))
@@ -739,6 +748,10 @@ function _quant_maplookup(::Type{U}, descs::Vector{QuantDesc}, formats, batch, p
             part = mine[c:min(c + ET_MAX_TABLES_PER_LAUNCH - 1, length(mine))]
             if fmt == 0
                 check(ccall((:et_quant_maplookup_prealloc, libembtab), Cint,
+                            (Cint, Ptr{QuantDesc}, Int32, Int64, Ptr{Cvoid}, Int64, UInt32, Ptr{Cvoid}),
+                            et_dtype(U), part, length(part), batch, p, ld, ET_FLAG_NONTEMPORAL, stream()))
+            elseif fmt == 3
+                check(ccall((:et_mx4_maplookup_prealloc, libembtab), Cint,
                             (Cint, Ptr{QuantDesc}, Int32, Int64, Ptr{Cvoid}, Int64, UInt32, Ptr{Cvoid}),
                             et_dtype(U), part, length(part), batch, p, ld, ET_FLAG_NONTEMPORAL, stream()))
             else

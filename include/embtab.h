@@ -838,6 +838,68 @@ int et_fp8_maplookup_prealloc(int dst_dtype, int format, const et_quant_desc* de
                               int64_t batch, void* dst, int64_t ld_dst, uint32_t flags,
                               void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * MXFP4 rows (inference only): OCP Microscaling FP4 — blocks of 32 E2M1 codes under one shared
+ * E8M0 power-of-two scale — in the layout of the quantised tables, addressed by et_quant_desc
+ * with bits == 4.  Row r (1-based) starts at table + (r-1)*ld_bytes; dim % 32 == 0 is required
+ * (anything else: ET_ERR_ARG).
+ *   payload  dim/2 bytes: feature 2k is the low nibble of byte k, feature 2k+1 the high nibble
+ *            (INT4's rule).
+ *   scales   dim/32 bytes: byte b scales features 32b .. 32b+31.
+ *            fused (hdr == NULL): bytes [payload, payload + dim/32) of the row;
+ *            ld_bytes >= payload + dim/32.
+ *            split (hdr != NULL): hdr is a device array of nrows entries of round_up(dim/32, 4)
+ *            bytes each; ld_bytes >= payload.
+ *            In both forms ld_bytes is a multiple of 4.
+ *   reads    no result depends on padding, and nothing outside nrows*ld_bytes of the table or
+ *            nrows*round_up(dim/32, 4) of hdr is read.  There is no per-row header and no bias.
+ *
+ * Element: a code is OCP E2M1, sign in bit 3, magnitude codes 0..7 = 0, 0.5, 1, 1.5, 2, 3, 4, 6;
+ * code 8 is -0.  Scale: a byte e in 0..254 means 2^(e-127); byte 255 is NaN (every feature of
+ * the block is NaN).
+ *
+ * Dequantisation:  v_f = E2M1(q_f) * 2^(e-127)  as a Float32.  The product is exact wherever it
+ * is representable: the smallest value, 0.5 * 2^-127 = 2^-128, is a Float32 subnormal and is
+ * kept, not flushed; only magnitudes 2, 3, 4 and 6 under e = 254 exceed Float32 and give +-Inf.
+ * There is no rounding anywhere in the decode, so a bag's Float32 result is the float kernels'
+ * result on the dequantised table bit for bit.
+ *
+ * Quantiser, per block of 32 (OCP MX v1.0 section 6.3); every step is exact or one Float32
+ * rounding:
+ *   amax = max_f |x_f|
+ *   e    = max(expfield(amax) - 2, 0)      expfield: the biased exponent field of the Float32
+ *          amax, so e = clamp(floor(log2 amax) - 2, -127, ..) + 127; a zero or subnormal amax
+ *          gives e = 0
+ *   y_f  = x_f * 2^(127-e)                 exact unless subnormal, which rounds to a zero code
+ *   q_f  = e2m1_rne(min(max(y_f, -6), 6))  clamp first, then one rounding, ties to the even
+ *          code; the sign of a zero is kept
+ * Values in (6 * 2^(e-127), 8 * 2^(e-127)) saturate at 6 (the floor rule of the standard).  A
+ * block holding a non-finite value gets unspecified contents (never a fault).  The quantiser
+ * writes the payload and the scales only, never the padding.
+ * ------------------------------------------------------------------------------- */
+
+/* Quantise `nrows` rows of a contiguous Float32 source (row r at src + r*ld_src, ld_src >= dim)
+ * into MXFP4 rows; scales == NULL writes the scale bytes fused behind the payload, otherwise
+ * into the split array.  ET_ERR_ARG: dim % 32 != 0, ld_bytes too small or not a multiple of 4,
+ * negative sizes, NULL src/table.  nrows == 0 is a no-op. */
+int et_mx4_quantize_rows(const float* src, int64_t ld_src, int64_t nrows, int32_t dim,
+                         void* table, int64_t ld_bytes, void* scales, void* stream);
+
+/* et_quant_maplookup_prealloc over MXFP4 tables: the same pooled sum (a COPY of the first row's
+ * v, the others added one at a time in index order in Float32, +0 for an empty bag or pool == 0,
+ * one RNE conversion to ET_F32 / ET_F16 / ET_BF16), the same descriptors (hdr is the split scale
+ * array), flags, destination types, ET_MAX_TABLES_PER_LAUNCH, out-of-range counting and argument
+ * rules, all checked before any device work.  An index outside 1..nrows is counted and adds +0
+ * to every feature whatever row 1 holds (a NaN scale byte included).  descs[t].bits != 4 or
+ * descs[t].dim % 32 != 0: ET_ERR_ARG.  Fixed-pool and ragged tables, fused and split scales may
+ * share a call; rows that are whole 16-byte vectors (table 16-byte aligned, ld_bytes % 16 == 0,
+ * at most 1024 payload bytes, a split array 4-byte aligned) take the vector kernel, every other
+ * shape a generic one with the same results.  Stream-ordered on the caller's stream only,
+ * allocates nothing, never synchronises: capturable. */
+int et_mx4_maplookup_prealloc(int dst_dtype, const et_quant_desc* descs, int32_t ntables,
+                              int64_t batch, void* dst, int64_t ld_dst, uint32_t flags,
+                              void* stream);
+
 /* Assemble the Preallocation concat from per-rank slabs after an all-gather
  * (table-wise sharding across GPUs, no counterpart in the single-process
  * reference): slab r is a (slab_ld x batch) column-major block at
