@@ -1720,6 +1720,9 @@ ET_OOB_READER(lookup)
 // MXFP4 rows (et_mx4_quantize_rows, et_mx4_maplookup_prealloc).
 #include "et_mx4.hip"
 
+// Weighted and mean-pooled bags over quantised tables (et_quant_weighted_maplookup_prealloc).
+#include "et_quant_weighted.hip"
+
 #ifdef ET_WG_TIMELINE
 // Profiling build only: copies the striped launch's workgroup records (2 x uint4 each)
 // to host memory; returns the number copied.

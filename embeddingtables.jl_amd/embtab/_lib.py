@@ -33,6 +33,7 @@ ET_FLAG_SGD_APPLY_ONLY = 64
 ET_FLAG_SGD_HOT_PASS = 128
 ET_FLAG_ADAGRAD_ROWWISE = 512
 ET_POOL_SUM, ET_POOL_MEAN = 0, 1
+ET_QUANT_INT, ET_FP8_E4M3, ET_FP8_E5M2, ET_QUANT_MXFP4 = 0, 1, 2, 3  # a quantised launch group
 ET_MAX_TABLES_PER_LAUNCH = 32
 ET_SGD_CHUNK = 256  # include/embtab.h: occurrences per chunk of the non-exact SGD
 ET_ABI_VERSION = 9
@@ -86,6 +87,7 @@ EXPORTS = (
     "et_fp8_maplookup_prealloc",
     "et_mx4_quantize_rows",
     "et_mx4_maplookup_prealloc",
+    "et_quant_weighted_maplookup_prealloc",
     "et_concat_slabs",
     "et_split_slabs",
     "et_push_cols",
@@ -282,6 +284,26 @@ class QuantDesc(ctypes.Structure):
     ]
 
 
+class QuantWeightedDesc(ctypes.Structure):
+    """et_quant_weighted_desc (include/embtab.h)."""
+
+    _fields_ = [
+        ("table", ctypes.c_void_p),
+        ("ld_bytes", ctypes.c_int64),
+        ("nrows", ctypes.c_int64),
+        ("dim", ctypes.c_int32),
+        ("bits", ctypes.c_int32),
+        ("hdr", ctypes.c_void_p),
+        ("idx", ctypes.c_void_p),
+        ("nnz", ctypes.c_int64),
+        ("colptr", ctypes.c_void_p),
+        ("dst_row_off", ctypes.c_int64),
+        ("weights", ctypes.c_void_p),
+        ("mode", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -340,6 +362,8 @@ def load() -> ctypes.CDLL:
         "et_fp8_maplookup_prealloc": ([c_int, c_int, vp, i32, i64, vp, i64, u32, vp], c_int),
         "et_mx4_quantize_rows": ([vp, i64, i64, i32, vp, i64, vp, vp], c_int),
         "et_mx4_maplookup_prealloc": ([c_int, vp, i32, i64, vp, i64, u32, vp], c_int),
+        "et_quant_weighted_maplookup_prealloc": ([c_int, c_int, vp, i32, i64, vp, i64, u32, vp],
+                                                 c_int),
         "et_concat_slabs": ([c_int, vp, i32, i64, i64, vp, vp, vp, i64, vp], c_int),
         "et_split_slabs": ([c_int, vp, i64, i64, i32, vp, vp, vp, i64, vp], c_int),
         "et_push_cols": ([c_int, vp, i64, i64, i64, i64, vp, i32, vp], c_int),

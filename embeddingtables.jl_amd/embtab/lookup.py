@@ -20,7 +20,8 @@ import threading
 import torch
 
 from . import _lib
-from .quant import QuantizedEmbedding, is_quantized_list, quant_descs, quant_launch
+from .quant import (QuantizedEmbedding, is_quantized_list, quant_descs, quant_launch,
+                    quant_weighted_groups, quant_weighted_launch)
 from .ragged import RaggedIndices, arithmetic_colptr
 from .tables import AbstractEmbeddingTable, ArgumentError, featuresize, example
 from .weighted import WeightedIndices, weighted_desc, weighted_launch
@@ -149,6 +150,10 @@ def lookup_(dst: torch.Tensor, A: AbstractEmbeddingTable, I: torch.Tensor,
     L = _lib.load()
     D, R = A.size()
     flags = _lib.ET_FLAG_NONTEMPORAL if nontemporal else 0
+    if isinstance(I, WeightedIndices) and isinstance(A, QuantizedEmbedding):
+        # a table made with weighted=True: one et_quant_weighted_maplookup_prealloc call
+        quant_weighted_launch(quant_weighted_groups([A], [I], [0], B), B, dst, _ld(dst), flags)
+        return dst
     if isinstance(I, WeightedIndices):  # weighted / mean bags: one table of the weighted entry
         descs = (_lib.WeightedDesc * 1)(weighted_desc(A, I, 0))
         weighted_launch(descs, 1, B, dst, _ld(dst), flags)
@@ -362,8 +367,39 @@ class PreallocationPlan:
         # own, each with its own first row; the others take the usual path exactly as they
         # would without them (two launches, so no existing result moves).
         self._wn, offs = 0, None
+        self._qw = None
         wpos = [t for t, i in enumerate(Is) if isinstance(i, WeightedIndices)]
-        if wpos:
+        qw = [t for t in wpos if isinstance(tables[t], QuantizedEmbedding)]
+        if qw:
+            # Quantised tables under weighted indices (tables made with weighted=True): one
+            # et_quant_weighted_maplookup_prealloc call per format present, each table with its
+            # own first row; the plain-index tables of the list take today's launches unchanged.
+            is_quantized_list(tables)  # a mix with float tables raises
+            if f16_fp32_acc:
+                raise ArgumentError("f16_fp32_acc belongs to Float16 tables: a quantised lookup "
+                                    "always sums in Float32")
+            offs, off = [], k
+            for A in tables:
+                offs.append(off)
+                off += featuresize(A)
+            for t in wpos:
+                _check_table(tables[t])
+                _check_idx(Is[t])
+            self._qw = quant_weighted_groups([tables[t] for t in wpos], [Is[t] for t in wpos],
+                                             [offs[t] for t in wpos], B)
+            self._wn = len(wpos)
+            self._wkeep = (dst, [tables[t] for t in wpos], [Is[t] for t in wpos])
+            self._wflags = _lib.ET_FLAG_NONTEMPORAL if nontemporal else 0
+            _lib.et_dtype(dst)
+            rest = [t for t in range(len(tables)) if t not in set(wpos)]
+            tables, Is = [tables[t] for t in rest], [Is[t] for t in rest]
+            offs = [offs[t] for t in rest]
+            self._dst, self._ld, self._B = dst, _ld(dst), B
+            self._quant = False
+            self._n = 0
+            if not tables:
+                return
+        elif wpos:
             if dst.dtype != dtype:
                 raise NotImplementedError(
                     "PreallocationStrategy(k, eltype=U) with weighted indices: the weighted "
@@ -395,14 +431,14 @@ class PreallocationPlan:
             if not tables:
                 return
         self._quant = is_quantized_list(tables)  # all quantised, or none (a mix raises)
-        if self._quant and wpos:
+        if self._quant and wpos and not qw:
             raise ArgumentError("quantised tables beside weighted indices in one maplookup")
         if self._quant:  # fixed-pool and ragged indices alike, one launch per format present
             if f16_fp32_acc:
                 raise ArgumentError("f16_fp32_acc belongs to Float16 tables: a quantised lookup "
                                     "always sums in Float32")
             self._keep = (dst, tables, Is)
-            self._descs = quant_descs(tables, Is, B, k)
+            self._descs = quant_descs(tables, Is, B, k, offs)
             self._n, self._B = len(tables), B
             self._flags = _lib.ET_FLAG_NONTEMPORAL if nontemporal else 0
             self._dst, self._ld = dst, _ld(dst)
@@ -434,7 +470,10 @@ class PreallocationPlan:
         """Launch on the current stream; returns the destination."""
         dst = self._dst
         if self._wn:  # the weighted / mean tables, then the others as ever
-            weighted_launch(self._wdescs, self._wn, self._B, dst, self._ld, self._wflags)
+            if self._qw is not None:
+                quant_weighted_launch(self._qw, self._B, dst, self._ld, self._wflags)
+            else:
+                weighted_launch(self._wdescs, self._wn, self._B, dst, self._ld, self._wflags)
             if self._n == 0:
                 return dst
         if self._quant:

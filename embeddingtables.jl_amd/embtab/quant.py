@@ -8,6 +8,11 @@ A ``QuantizedEmbedding`` is an inference-only table: ``lookup`` / ``maplookup`` 
 ``PreallocationPlan`` accept it under every strategy (one et_quant_maplookup_prealloc,
 et_fp8_maplookup_prealloc or et_mx4_maplookup_prealloc launch per format in the call),
 ``rrule``, ``update_``, ``PhasedUpdate`` and the sharding classes refuse it.
+
+A table made with ``weighted=True`` (or ``Q.accept_weighted()``) also takes
+``WeightedIndices``: per-sample weights and ``mode="mean"``, one
+et_quant_weighted_maplookup_prealloc call per format present.  Without the flag such a lookup
+raises ``ArgumentError`` as it always did.
 """
 from __future__ import annotations
 
@@ -74,12 +79,15 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
     ``dim * bits / 8`` payload bytes first and, when ``header`` is None, the Float16 scale
     and bias right behind them (the fused header).  ``header`` is a contiguous ``(R, 4)``
     uint8 or ``(R, 2)`` float16 tensor (scale, bias) for the split form.  ``ld_bytes`` (the
-    row stride) must be a multiple of 4.  The logical element type is Float32."""
+    row stride) must be a multiple of 4.  The logical element type is Float32.
+    ``weighted=True`` makes the table accept ``WeightedIndices`` (Float32 weights, or
+    ``mode="mean"``); it changes nothing about the storage."""
 
     lookup_type = Dynamic
 
     def __init__(self, packed: torch.Tensor, dim: int, bits: int,
-                 header: torch.Tensor | None = None, format: str = "int"):
+                 header: torch.Tensor | None = None, format: str = "int",
+                 weighted: bool = False):
         if not isinstance(packed, torch.Tensor) or packed.dim() != 2 or packed.dtype != torch.uint8:
             raise ArgumentError("QuantizedEmbedding expects a 2-D (R, ld_bytes) uint8 tensor")
         if isinstance(dim, bool) or not isinstance(dim, int) or dim < 1:
@@ -120,6 +128,11 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
         self.bits = bits
         self.format = format
         self.ld_bytes = ld
+        self.weighted = bool(weighted)
+
+    def accept_weighted(self) -> "QuantizedEmbedding":
+        """A view of the same storage (no copy) that takes ``WeightedIndices``."""
+        return type(self)(self.packed, self.dim, self.bits, self.header, self.format, weighted=True)
 
     def __repr__(self):
         kind = f"INT{self.bits}" if self.format == "int" else \
@@ -129,12 +142,13 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
 
     @classmethod
     def quantize(cls, src, bits: int | None = None, ld_bytes: int | None = None,
-                 split_header: bool = False, format: str = "int") -> "QuantizedEmbedding":
+                 split_header: bool = False, format: str = "int",
+                 weighted: bool = False) -> "QuantizedEmbedding":
         """Quantise a Float32 ``(R, D)`` tensor or float table on the device (et_quantize_rows,
         et_fp8_quantize_rows for ``format="e4m3"`` / ``"e5m2"`` or et_mx4_quantize_rows for
         ``"mxfp4"``: include/embtab.h's quantisers).  ``bits`` defaults to the format's own (4 for
         MXFP4, 8 otherwise); ``ld_bytes`` to the payload (+ the header or scale bytes when fused)
-        rounded up to 16; padding bytes are zero."""
+        rounded up to 16; padding bytes are zero.  ``weighted``: see the class."""
         bits = check_format(format, bits)
         if isinstance(src, AbstractEmbeddingTable):
             if isinstance(src, QuantizedEmbedding):
@@ -173,7 +187,7 @@ class QuantizedEmbedding(AbstractEmbeddingTable):
         else:
             _lib.check(L.et_fp8_quantize_rows(FORMATS[format][0], src.data_ptr(), ld_src, R, D,
                                               packed.data_ptr(), ld, hdr, stream))
-        return cls(packed, D, bits, header, format)
+        return cls(packed, D, bits, header, format, weighted=weighted)
 
     # --- the table contract -------------------------------------------------------------
     def size(self):
@@ -274,14 +288,17 @@ def is_quantized_list(tables) -> bool:
     return True
 
 
-def quant_descs(tables, Is, B: int, k: int):
+def quant_descs(tables, Is, B: int, k: int, offs=None):
     """The et_quant_desc arrays of a list of quantised tables (fixed-pool and ragged indices),
-    one per format present: what `quant_launch` takes."""
+    one per format present: what `quant_launch` takes.  `offs` gives every table's first
+    destination row (default: back to back from `k`)."""
     from .lookup import _check_idx, _ld, _trailing_size
 
     descs = (_lib.QuantDesc * len(tables))()
     off = k
     for t, (A, i) in enumerate(zip(tables, Is)):
+        if offs is not None:
+            off = offs[t]
         if not A.packed.is_cuda:
             raise ArgumentError("the HIP engine needs tables in device memory")
         _check_idx(i)
@@ -338,3 +355,40 @@ def quant_launch(groups, B: int, dst: torch.Tensor, ld_dst: int, flags: int) -> 
             else:
                 _lib.check(L.et_fp8_maplookup_prealloc(dt, fmt, part, m, B, dst.data_ptr(),
                                                        ld_dst, flags, stream))
+
+
+def quant_weighted_groups(tables, Is, offs, B: int):
+    """[(launch group of FORMATS, et_quant_weighted_desc array)] of quantised tables under
+    ``WeightedIndices``, one array per format present, every table at its own first destination
+    row ``offs[t]``: what `quant_weighted_launch` takes."""
+    by = {}
+    for t, (A, I, off) in enumerate(zip(tables, Is, offs)):
+        if not A.packed.is_cuda or not I.is_cuda:
+            raise ArgumentError("the HIP engine needs tables and indices in device memory")
+        I.check_for(A)
+        if I.batch != B:
+            raise ArgumentError(f"table {t}: batch {I.batch} != {B}")
+        D, R = A.size()
+        r = I.ragged
+        desc = _lib.QuantWeightedDesc(
+            A.packed.data_ptr(), A.ld_bytes, R, D, A.bits,
+            A.header.data_ptr() if A.header is not None else None, r.values.data_ptr(), r.nnz,
+            r.colptr.data_ptr(), off, I.weights.data_ptr() if I.weights is not None else None,
+            _lib.ET_POOL_MEAN if I.mode == "mean" else _lib.ET_POOL_SUM, 0)
+        by.setdefault(FORMATS[A.format][0], []).append(desc)
+    return [(fmt, (_lib.QuantWeightedDesc * len(v))(*v)) for fmt, v in sorted(by.items())]
+
+
+def quant_weighted_launch(groups, B: int, dst: torch.Tensor, ld_dst: int, flags: int) -> None:
+    """et_quant_weighted_maplookup_prealloc over the groups of `quant_weighted_groups`, at most
+    ET_MAX_TABLES_PER_LAUNCH a call."""
+    if dst.dtype not in OUT_DTYPES:
+        raise ArgumentError(f"a quantised lookup writes Float32, Float16 or BFloat16, not {dst.dtype}")
+    L = _lib.load()
+    step, size = _lib.ET_MAX_TABLES_PER_LAUNCH, ctypes.sizeof(_lib.QuantWeightedDesc)
+    dt, stream = _lib.et_dtype(dst), _lib.stream_handle(dst.device)
+    for fmt, descs in groups:
+        for c in range(0, len(descs), step):
+            _lib.check(L.et_quant_weighted_maplookup_prealloc(
+                dt, fmt, ctypes.addressof(descs) + c * size, min(step, len(descs) - c), B,
+                dst.data_ptr(), ld_dst, flags & _lib.ET_FLAG_NONTEMPORAL, stream))

@@ -115,9 +115,11 @@ class WeightedIndices:
 
     def check_for(self, A) -> None:
         """The table-dependent checks, made at the call."""
-        if isinstance(A, QuantizedEmbedding):
-            raise ArgumentError("weighted / mean bags over a quantised table are not supported")
-        C = acc_dtype(A.dtype)
+        if isinstance(A, QuantizedEmbedding) and not A.weighted:
+            raise ArgumentError("weighted / mean bags over a quantised table are not supported "
+                                "unless the table accepts them: QuantizedEmbedding(..., "
+                                "weighted=True) or Q.accept_weighted()")
+        C = acc_dtype(A.dtype)  # Float32 for a quantised table
         if self.weights is not None and self.weights.dtype != C:
             raise ArgumentError(f"weights of {self.weights.dtype} with a {A.dtype} table: they "
                                 f"must be {C}")

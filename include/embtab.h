@@ -900,6 +900,75 @@ int et_mx4_maplookup_prealloc(int dst_dtype, const et_quant_desc* descs, int32_t
                               int64_t batch, void* dst, int64_t ld_dst, uint32_t flags,
                               void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Weighted and mean-pooled bags over quantised tables (inference only), every row format
+ * above.  The arithmetic is the composition of the two contracts, with C = Float32:
+ *   v_k  the row's dequantised Float32 value under its format's own rule.  INT and FP8:
+ *        fma(q, scale, bias), an exact product and one rounding.  MXFP4: the exact scaled
+ *        decode.
+ *   sum mode with weights, for a bag [lo, hi):
+ *        acc = w_lo * v_lo;  for k = lo+1 .. hi-1:  t = w_k * v_k;  acc = acc + t
+ *        in index order; each product and each add is rounded once in Float32, nothing is
+ *        fused between them (the multiply is never folded into the scale or the bias).
+ *        out = O(acc), one RNE conversion to ET_F32 / ET_F16 / ET_BF16.
+ *   An index outside 1..nrows is counted and takes v = +0 whatever row 1 holds, a NaN FP8
+ *        code or a NaN MXFP4 scale byte included.  It is still multiplied, so the zero's sign
+ *        follows the weight.
+ *   weights == NULL: no products.  The sum starts from a COPY of the first row's v; the result
+ *        equals et_quant_ / et_fp8_ / et_mx4_maplookup_prealloc on the same ragged bags bit
+ *        for bit, and so does the result with every weight 1.0.
+ *   mean mode: weights must be NULL (ET_ERR_UNSUPPORTED otherwise); out = O(acc / float(hi - lo)),
+ *        one correctly rounded division; out-of-range entries count in the length.
+ *   An empty bag writes +0.
+ * Consequence: the ET_F32 result equals et_weighted_maplookup_prealloc on the dequantised
+ * Float32 table bit for bit.
+ *
+ * Bags are always ragged (idx, colptr, the capacity nnz, et_ragged_desc's clamping, each
+ * clamped bound counted); a fixed-pool P x B index rides as the arithmetic colptr 1 + P*(0:B).
+ * Reads: no weight outside [0, nnz) is read, nor at an entry no bag covers; the table and
+ * header (scale) read rules are those of each format.  There is no backward entry: quantised
+ * tables stay inference only.
+ * ------------------------------------------------------------------------------- */
+
+/* The launch groups of et_quant_weighted_maplookup_prealloc's `format`, beside ET_FP8_E4M3 (1)
+ * and ET_FP8_E5M2 (2). */
+#define ET_QUANT_INT 0   /* INT8 / INT4 rows (et_quant_maplookup_prealloc's tables) */
+#define ET_QUANT_MXFP4 3 /* MXFP4 rows (et_mx4_maplookup_prealloc's tables) */
+
+/* One table of a weighted / mean lookup over quantised rows. */
+typedef struct et_quant_weighted_desc {
+    const void* table;     /* as et_quant_desc, per format */
+    int64_t ld_bytes;
+    int64_t nrows;
+    int32_t dim;
+    int32_t bits;
+    const void* hdr;       /* split header / split MXFP4 scales, or NULL */
+    const int64_t* idx;    /* device, the bags' indices back to back, 1-based Int64 */
+    int64_t nnz;           /* capacity of idx and of weights */
+    const int64_t* colptr; /* device, batch + 1 entries, required */
+    int64_t dst_row_off;   /* as in et_lookup_desc */
+    const float* weights;  /* device, nnz Float32 entries, or NULL (unweighted) */
+    int32_t mode;          /* ET_POOL_SUM or ET_POOL_MEAN */
+    int32_t reserved;      /* 0 */
+} et_quant_weighted_desc;
+
+/* Fused weighted / mean lookup + concat over quantised tables of ONE format (ET_QUANT_INT,
+ * ET_FP8_E4M3, ET_FP8_E5M2 or ET_QUANT_MXFP4; anything else: ET_ERR_UNSUPPORTED) into
+ * dst[desc[t].dst_row_off + (0:dim_t-1), j], semantics above.  Weighted, unweighted and mean
+ * tables may share a call, and so may fused and split headers (and INT8 with INT4).  Rows that
+ * are whole 16-byte vectors (each format's own rule) take the vector kernel, every other shape
+ * a generic one with the same results.  Flags: ET_FLAG_NONTEMPORAL only.  Every argument error
+ * is reported before any device work: the per-format rules of et_quant_ / et_fp8_ /
+ * et_mx4_maplookup_prealloc (bits, dim, ld_bytes, dim % 32 for MXFP4, rows outside ld_dst, too
+ * many tables, the destination type and flags), a NULL colptr, a mode that is neither of the
+ * two, weights that are not 4-byte aligned (ET_ERR_ARG) and weights with ET_POOL_MEAN
+ * (ET_ERR_UNSUPPORTED).  Stream-ordered on the caller's stream only, allocates nothing, never
+ * synchronises: capturable.  batch == 0 is a no-op. */
+int et_quant_weighted_maplookup_prealloc(int dst_dtype, int format,
+                                         const et_quant_weighted_desc* descs, int32_t ntables,
+                                         int64_t batch, void* dst, int64_t ld_dst, uint32_t flags,
+                                         void* stream);
+
 /* Assemble the Preallocation concat from per-rank slabs after an all-gather
  * (table-wise sharding across GPUs, no counterpart in the single-process
  * reference): slab r is a (slab_ld x batch) column-major block at
