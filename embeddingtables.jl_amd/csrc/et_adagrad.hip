@@ -556,7 +556,8 @@ inline bool ranges_overlap(uintptr_t a, uint64_t na, uintptr_t b, uint64_t nb) {
 // Descriptor checks (host only); *n_out = occurrences of all tables with work, *pdim_out the
 // largest dim rounded up to a 16-byte row of floats.
 inline int validate_adagrad(int dtype, const et_adagrad_desc* descs, int ntables, bool rowwise,
-                            int64_t* n_out, int* pdim_out, bool need_ptrs) {
+                            int64_t* n_out, int* pdim_out, bool need_ptrs,
+                            const char* sname = "state") {
     if (ntables < 0) return fail(ET_ERR_ARG, "negative ntables");
     if (ntables > ET_MAX_TABLES_PER_LAUNCH)
         return fail(ET_ERR_ARG, "at most %d tables per update call", ET_MAX_TABLES_PER_LAUNCH);
@@ -575,14 +576,14 @@ inline int validate_adagrad(int dtype, const et_adagrad_desc* descs, int ntables
         if (!ada_work(d)) continue;
         if (need_ptrs) {
             if (!d.idx || !d.table || !d.delta) return fail(ET_ERR_ARG, "table %d: NULL", t);
-            if (!d.state) return fail(ET_ERR_ARG, "table %d: state is NULL", t);
+            if (!d.state) return fail(ET_ERR_ARG, "table %d: %s is NULL", t, sname);
         }
         if (!ada_ragged(d) && d.ld_idx < d.pool)
             return fail(ET_ERR_ARG, "table %d: ld_idx < pool", t);
         if (d.ld_table < d.dim || d.ld_delta < d.dim)
             return fail(ET_ERR_ARG, "table %d: leading dimension < dim", t);
         if (!rowwise && d.ld_state < d.dim)
-            return fail(ET_ERR_ARG, "table %d: ld_state < dim", t);
+            return fail(ET_ERR_ARG, "table %d: ld_%s < dim", t, sname);
         if (need_ptrs && d.nrows > 0) {
             const uint64_t sbytes =
                 rowwise ? (uint64_t)d.nrows * cs
@@ -593,7 +594,7 @@ inline int validate_adagrad(int dtype, const et_adagrad_desc* descs, int ntables
                     ? (uint64_t)((d.nrows + d.cols_per_page - 1) / d.cols_per_page) * 8u
                     : ((uint64_t)(d.nrows - 1) * (uint64_t)d.ld_table + (uint64_t)d.dim) * es;
             if (ranges_overlap((uintptr_t)d.state, sbytes, (uintptr_t)d.table, tbytes))
-                return fail(ET_ERR_ARG, "table %d: state overlaps the table", t);
+                return fail(ET_ERR_ARG, "table %d: %s overlaps the table", t, sname);
         }
         n += ada_occurrences(d);
         if (n >= 0x7fffffffll) return fail(ET_ERR_ARG, "too many occurrences");
@@ -690,17 +691,28 @@ int launch_adagrad(const AdaRun& r, C eta, C eps) {
     return ET_OK;
 }
 
-// The front of the pipeline, shared with et_weighted_adagrad: descriptor checks, the workspace,
-// the tables packed as vector or fixed-pool indices, the bag id of every ragged entry and
-// group_occurrences.  run.n == 0 on return means there is nothing to launch.
-inline int prepare_adagrad(int dtype, const et_adagrad_desc* descs, int ntables, bool rowwise,
-                           void* workspace, int64_t ws_bytes, void* stream, AdaRun& run) {
-    int rc = validate_adagrad(dtype, descs, ntables, rowwise, &run.n, &run.pdim, true);
-    if (rc != ET_OK) return rc;
-    if (run.n == 0) return ET_OK;
-    run.w = carve_adagrad_ws(static_cast<char*>(workspace), run.n, run.pdim);
-    if (!workspace || ws_bytes < run.w.bytes)
-        return fail(ET_ERR_WORKSPACE, "workspace of %lld bytes needed", (long long)run.w.bytes);
+// What et_sparse_adam's front does differently from et_sparse_adagrad's (whose values are the
+// defaults): tables kept off the vector kernels for a reason the state pointer does not show,
+// the largest dim the vector kernels take, and buffers cleared by a kernel instead of a
+// memset node, so that a captured call holds kernel nodes only.
+struct AdaFrontOpts {
+    uint32_t no_vec = 0;
+    int vec_max_dim = 2048;
+    bool kernel_clears = false;
+};
+
+__global__ __launch_bounds__(256) void k_clear_u32(uint32_t* __restrict__ p, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        p[i] = 0u;
+}
+
+// The descriptor packing and index phase of every optimiser of this family (run.n, run.pdim
+// and run.w are set): the tables packed as vector or fixed-pool indices, the bag id of every
+// ragged entry and group_occurrences.  d.state / d.ld_state are the element-wise state the
+// vector kernels' alignment rule looks at (`rowwise`: one value per column).
+inline int pack_adagrad_tables(int dtype, const et_adagrad_desc* descs, int ntables, bool rowwise,
+                               void* stream, AdaRun& run, const AdaFrontOpts& fo) {
+    int rc;
     run.ntables = ntables;
     run.s = static_cast<hipStream_t>(stream);
 
@@ -745,7 +757,8 @@ inline int prepare_adagrad(int dtype, const et_adagrad_desc* descs, int ntables,
         }
         // the vector kernels: Float32 rows, gradient rows and state rows of 16-byte multiples
         const bool vec = dtype == ET_F32 && (a.cols_per_page > 0 || aligned16(a.table)) &&
-                         a.ld_table % 4 == 0 && a.dim % 4 == 0 && a.dim <= 2048 &&
+                         a.ld_table % 4 == 0 && a.dim % 4 == 0 && a.dim <= fo.vec_max_dim &&
+                         !((fo.no_vec >> t) & 1u) &&
                          aligned16(a.delta) && a.ld_delta % 4 == 0 &&
                          (rowwise ? ((uintptr_t)a.state & 3u) == 0
                                   : aligned16(a.state) && a.ld_state % 4 == 0);
@@ -759,11 +772,32 @@ inline int prepare_adagrad(int dtype, const et_adagrad_desc* descs, int ntables,
     run.sent = ro;  // key of out-of-range indices (sorts last)
 
     if (run.ap.ragged) {
-        ET_HIP_CHECK(hipMemsetAsync(run.w.bag, 0, (size_t)run.n * 4, run.s));
+        if (fo.kernel_clears) {
+            const int64_t cb = cdiv64(run.n, 1024);
+            hipLaunchKernelGGL(k_clear_u32, dim3((unsigned)(cb < 1024 ? cb : 1024)), dim3(256), 0,
+                               run.s, run.w.bag, run.n);
+            ET_LAUNCH_CHECK("k_clear_u32");
+        } else {
+            ET_HIP_CHECK(hipMemsetAsync(run.w.bag, 0, (size_t)run.n * 4, run.s));
+        }
         rc = launch_ragged_bag_ids<uint32_t>(ba, ntables, max_batch, run.w.bag, run.s);
         if (rc != ET_OK) return rc;
     }
-    return group_occurrences(pack, ntables, run.n, run.sent, kChunk, run.w.u, run.gr, run.s);
+    return group_occurrences(pack, ntables, run.n, run.sent, kChunk, run.w.u, run.gr, run.s, 0,
+                             nullptr, nullptr, fo.kernel_clears);
+}
+
+// The front of the pipeline, shared with et_weighted_adagrad: descriptor checks, the workspace,
+// then pack_adagrad_tables.  run.n == 0 on return means there is nothing to launch.
+inline int prepare_adagrad(int dtype, const et_adagrad_desc* descs, int ntables, bool rowwise,
+                           void* workspace, int64_t ws_bytes, void* stream, AdaRun& run) {
+    int rc = validate_adagrad(dtype, descs, ntables, rowwise, &run.n, &run.pdim, true);
+    if (rc != ET_OK) return rc;
+    if (run.n == 0) return ET_OK;
+    run.w = carve_adagrad_ws(static_cast<char*>(workspace), run.n, run.pdim);
+    if (!workspace || ws_bytes < run.w.bytes)
+        return fail(ET_ERR_WORKSPACE, "workspace of %lld bytes needed", (long long)run.w.bytes);
+    return pack_adagrad_tables(dtype, descs, ntables, rowwise, stream, run, AdaFrontOpts{});
 }
 
 }  // namespace et

@@ -2736,13 +2736,22 @@ inline int launch_chain_plan(const UpdatePack& pack, int ntables, int64_t n, uin
     return ET_OK;
 }
 
+__global__ __launch_bounds__(64) void k_clear_counters(uint32_t* __restrict__ counters) {
+    if (threadIdx.x < kCntSlots) counters[threadIdx.x] = 0u;
+}
+
 // Steps 1-4: the sorted pairs (`out`), segments, chunks and chunk records of n occurrences
 // in the workspace; with a hot mask and list, the hot columns picked and retired too.
 inline int group_occurrences(const UpdatePack& pack, int ntables, int64_t n, uint32_t sent,
                              uint32_t chunk, const UpdateWs& w, Grouped& out, hipStream_t s,
                              uint32_t hot_mask = 0, const HotList* hl = nullptr,
-                             int64_t* const* snaps = nullptr) {
-    ET_HIP_CHECK(hipMemsetAsync(w.counters, 0, 4 * kCntSlots, s));
+                             int64_t* const* snaps = nullptr, bool kernel_clear = false) {
+    if (kernel_clear) {  // a kernel node instead of a memset node (et_sparse_adam)
+        hipLaunchKernelGGL(k_clear_counters, dim3(1), dim3(64), 0, s, w.counters);
+        ET_LAUNCH_CHECK("k_clear_counters");
+    } else {
+        ET_HIP_CHECK(hipMemsetAsync(w.counters, 0, 4 * kCntSlots, s));
+    }
     KeyGrid kg;
     kg.blk_off[0] = 0;
     kg.vec = 0;
@@ -3758,6 +3767,9 @@ extern "C" int et_update_indexed(int dtype, void* table, int64_t ld_table,
 
 // Sparse AdaGrad over weighted gradients (et_weighted_adagrad): chunk kernels, entry points.
 #include "et_weighted_adagrad.hip"
+
+// Sparse Adam (et_sparse_adam): kernels and entry points.
+#include "et_adam.hip"
 
 // Split sparse SGD over ragged and weighted gradients (et_ragged_sgd_split): kernels, entries.
 #include "et_ragged_sgd_split.hip"

@@ -17,7 +17,7 @@ from .weighted import WeightedIndices
 from .lookup import (AbstractExecutionStrategy, DefaultStrategy, NoTangent,
                      PreallocationPlan, PreallocationStrategy, SimpleParallelStrategy, colwrap, destination, lookup,
                      lookup_, maplookup, maplookup_)
-from .update import (AbstractIndexer, AdaGrad, DenseIndexer, Descent, Indexer, IndexerView, PhasedUpdate,
+from .update import (AbstractIndexer, AdaGrad, Adam, DenseIndexer, Descent, Indexer, IndexerView, PhasedUpdate,
                      SparseEmbeddingUpdate, SparseIndexer, ensemble_update, gettranslations,
                      index_, optimise_update_, rrule, uncompress, update_)
 
@@ -32,5 +32,5 @@ __all__ = [
     "rrule", "Descent", "AbstractIndexer", "Indexer", "SparseIndexer", "DenseIndexer",
     "IndexerView", "index_", "gettranslations", "update_", "optimise_update_",
     "ensemble_update", "PhasedUpdate", "EmbtabError", "check_errors",
-    "RaggedIndices", "AdaGrad", "QuantizedEmbedding", "WeightedIndices",
+    "RaggedIndices", "AdaGrad", "QuantizedEmbedding", "WeightedIndices", "Adam",
 ]

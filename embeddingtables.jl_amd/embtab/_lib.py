@@ -32,6 +32,8 @@ ET_FLAG_SGD_INDEX_ONLY = 32
 ET_FLAG_SGD_APPLY_ONLY = 64
 ET_FLAG_SGD_HOT_PASS = 128
 ET_FLAG_ADAGRAD_ROWWISE = 512
+ET_FLAG_ADAM_ROWWISE = 512  # the same bit: one row-wise flag per optimiser family
+ET_ADAM_VEC_MAX_DIM = 1024
 ET_POOL_SUM, ET_POOL_MEAN = 0, 1
 ET_QUANT_INT, ET_FP8_E4M3, ET_FP8_E5M2, ET_QUANT_MXFP4 = 0, 1, 2, 3  # a quantised launch group
 ET_MAX_TABLES_PER_LAUNCH = 32
@@ -81,6 +83,8 @@ EXPORTS = (
     "et_weighted_adagrad",
     "et_ragged_sgd_split_workspace_size",
     "et_ragged_sgd_split",
+    "et_adam_workspace_size",
+    "et_sparse_adam",
     "et_quantize_rows",
     "et_quant_maplookup_prealloc",
     "et_fp8_quantize_rows",
@@ -264,6 +268,18 @@ class WeightedAdaGradDesc(ctypes.Structure):
     _fields_ = AdaGradDesc._fields_ + [("weights", ctypes.c_void_p)]
 
 
+class AdamDesc(ctypes.Structure):
+    """et_adam_desc (include/embtab.h): et_adagrad_desc up to nnz, the moments, the step."""
+
+    _fields_ = AdaGradDesc._fields_[:13] + [
+        ("m", ctypes.c_void_p),
+        ("ld_m", ctypes.c_int64),
+        ("v", ctypes.c_void_p),
+        ("ld_v", ctypes.c_int64),
+        ("step", ctypes.c_void_p),
+    ]
+
+
 class QuantDesc(ctypes.Structure):
     """et_quant_desc (include/embtab.h)."""
 
@@ -356,6 +372,8 @@ def load() -> ctypes.CDLL:
         "et_weighted_adagrad": ([c_int, vp, i32, dbl, dbl, u32, vp, i64, vp], c_int),
         "et_ragged_sgd_split_workspace_size": ([vp, i32, vp], c_int),
         "et_ragged_sgd_split": ([c_int, vp, i32, dbl, u32, vp, i64, vp], c_int),
+        "et_adam_workspace_size": ([vp, i32, vp], c_int),
+        "et_sparse_adam": ([c_int, vp, i32, dbl, dbl, dbl, dbl, u32, vp, i64, vp], c_int),
         "et_quantize_rows": ([vp, i64, i64, i32, i32, vp, i64, vp, vp], c_int),
         "et_quant_maplookup_prealloc": ([c_int, vp, i32, i64, vp, i64, u32, vp], c_int),
         "et_fp8_quantize_rows": ([c_int, vp, i64, i64, i32, vp, i64, vp, vp], c_int),

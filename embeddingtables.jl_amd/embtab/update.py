@@ -254,6 +254,71 @@ class AdaGrad:
         return s
 
 
+class Adam:
+    """Sparse Adam (et_sparse_adam, include/embtab.h states the arithmetic): lazy, as
+    ``torch.optim.SparseAdam`` — only the columns a call touches move.  Per updated column
+    ``m' = b1*m + (1-b1)*g``, ``v' = b2*v + (1-b2)*g*g`` and
+    ``w' = w - eta * (m'/c1) / (sqrt(v'/c2) + eps)``; with ``rowwise=True`` ``m`` stays
+    element-wise and ``v`` is one value per column fed with ``mean(g*g)`` (FBGEMM's partial
+    row-wise Adam).  Beyond the reference, whose only optimiser is Descent.
+
+    The state lives in this object, per table object.  ``state(table)`` is ``(m, v)``: ``m`` is
+    ``(R, D)``, ``v`` is ``(R, D)`` or ``(R,)`` row-wise, zeros of Float32 (Float64 for Float64
+    tables), each one contiguous allocation whatever the table's storage.  ``step(table)`` is
+    the two-element device tensor ``{beta1^t, beta2^t}``, ``{1, 1}`` at first: the kernels
+    advance it themselves (one multiply per call) and take the bias corrections
+    ``c = 1 - beta^t`` from it, so a replayed HIP graph advances the step as an eager call does.
+    ``set_state(table, m, v)`` installs caller-owned tensors instead (row blocks of wider ones
+    are fine: unit feature stride, any row stride >= D)."""
+
+    def __init__(self, eta: float = 1e-3, beta=(0.9, 0.999), eps: float = 1e-8,
+                 rowwise: bool = False):
+        self.eta = float(eta)
+        self.beta = (float(beta[0]), float(beta[1]))
+        if not all(0.0 <= b < 1.0 for b in self.beta):
+            raise ArgumentError(f"beta {self.beta} outside [0, 1)")
+        self.eps = float(eps)
+        self.rowwise = bool(rowwise)
+        self._state = weakref.WeakKeyDictionary()
+        self._step = weakref.WeakKeyDictionary()
+
+    def __repr__(self):
+        return f"Adam({self.eta}, {self.beta}, {self.eps}{', rowwise' if self.rowwise else ''})"
+
+    _state_dtype = staticmethod(AdaGrad._state_dtype)
+
+    def _shapes(self, table):
+        D, R = table.size()
+        return (R, D), ((R,) if self.rowwise else (R, D))
+
+    def state(self, table: AbstractEmbeddingTable):
+        s = self._state.get(table)
+        if s is None:
+            s = tuple(torch.zeros(shape, dtype=self._state_dtype(table), device=table.device)
+                      for shape in self._shapes(table))
+            self._state[table] = s
+        return s
+
+    def step(self, table: AbstractEmbeddingTable) -> torch.Tensor:
+        s = self._step.get(table)
+        if s is None:
+            s = torch.ones(2, dtype=self._state_dtype(table), device=table.device)
+            self._step[table] = s
+        return s
+
+    def set_state(self, table: AbstractEmbeddingTable, m: torch.Tensor, v: torch.Tensor):
+        for name, s, shape in zip("mv", (m, v), self._shapes(table)):
+            if tuple(s.shape) != shape or s.dtype != self._state_dtype(table):
+                raise ArgumentError(f"{name} of shape {tuple(s.shape)} / {s.dtype}, expected "
+                                    f"{shape} / {self._state_dtype(table)}")
+            if s.device != table.device:
+                raise ArgumentError(f"{name} and table live on different devices")
+            if s.numel() > 0 and s.stride(-1) != 1:
+                raise ArgumentError(f"{name} features must be contiguous")
+        self._state[table] = (m, v)
+        return m, v
+
+
 # --- workspaces ------------------------------------------------------------------------------
 
 _ws_cache: "collections.OrderedDict" = collections.OrderedDict()
@@ -695,26 +760,33 @@ def update_(*args, nontemporal: bool | None = None, exact: bool | None = None,
       et_weighted_adagrad, grouped the same way: a hot column is ordered partial sums of
       ET_SGD_CHUNK entries, not one serial chain.  ``nontemporal``
       is its only keyword: ``exact``, ``hot_pass``, ``f16_fp32_acc``, ``split``, ``indexer`` /
-      ``indexers`` and ``telemetry_cb`` belong to the SGD and raise ``ArgumentError``."""
+      ``indexers`` and ``telemetry_cb`` belong to the SGD and raise ``ArgumentError``.
+    * ``update_(opt::Adam, table, grad)`` and ``update_(opt::Adam, tables, grads)`` — sparse
+      Adam (et_sparse_adam), fixed-pool and ragged gradients in the same call, grouped as for
+      AdaGrad, with the same keyword rules; a gradient that carries ``weights`` raises
+      ``ArgumentError``.  The moments and the step state are allocated outside the C call, so
+      they must exist before ``update_`` is captured into a HIP graph: call ``opt.state(A)``
+      and ``opt.step(A)`` first, or run one eager step."""
     for a in args[:2]:  # the table(s): first or second argument in every form
         if isinstance(a, (AbstractEmbeddingTable, list, tuple)):
             refuse_quantized(a, "update_")
-    if args and isinstance(args[0], AdaGrad):
+    if args and isinstance(args[0], (AdaGrad, Adam)):
         refused = {"exact": exact is not None, "f16_fp32_acc": bool(f16_fp32_acc),
                    "hot_pass": bool(hot_pass), "split": bool(split),
                    "indexer / indexers (positional)": len(args) > 3}
         refused.update({k: True for k in kw})
         for name, given in refused.items():
             if given:
-                raise ArgumentError(f"update_ with AdaGrad takes no `{name}`: nontemporal is "
-                                    "its only keyword")
+                raise ArgumentError(f"update_ with {type(args[0]).__name__} takes no `{name}`: "
+                                    "nontemporal is its only keyword")
         if len(args) < 3:
             raise ArgumentError("update_(opt, table, grad) or update_(opt, tables, grads)")
         nt = True if nontemporal is None else bool(nontemporal)
+        run = _update_adam if isinstance(args[0], Adam) else _update_adagrad
         if isinstance(args[1], AbstractEmbeddingTable):
-            _update_adagrad(args[0], [args[1]], [args[2]], nt)
+            run(args[0], [args[1]], [args[2]], nt)
         else:
-            _update_adagrad(args[0], list(args[1]), list(args[2]), nt)
+            run(args[0], list(args[1]), list(args[2]), nt)
         return None
     if split:
         if not (args and isinstance(args[0], Descent)):
@@ -1054,6 +1126,56 @@ def _update_adagrad(opt: AdaGrad, tables, grads, nontemporal: bool):
             ncall += 1
 
 
+def _adam_desc(opt: Adam, table, grad: SparseEmbeddingUpdate) -> _lib.AdamDesc:
+    m, v = opt.state(table)
+    ld = lambda s: int(s.stride(0)) if s.shape[0] > 1 else int(s.shape[1])
+    tail = (m.data_ptr(), ld(m), v.data_ptr(), 1 if opt.rowwise else ld(v),
+            opt.step(table).data_ptr())
+    if isinstance(grad.indices, RaggedIndices):
+        r = _ragged_update_desc(table, grad)
+        return _lib.AdamDesc(r.table, r.ld_table, r.nrows, r.dim, 1, r.delta, r.ld_delta, r.idx,
+                             1, r.batch, r.cols_per_page, r.colptr, r.nnz, *tail)
+    u = _update_desc(table, grad)
+    return _lib.AdamDesc(u.table, u.ld_table, u.nrows, u.dim, u.pool, u.delta, u.ld_delta, u.idx,
+                         u.ld_idx, u.batch, u.cols_per_page, None, 0, *tail)
+
+
+def _update_adam(opt: Adam, tables, grads, nontemporal: bool):
+    """One et_sparse_adam call per element type and at most ET_MAX_TABLES_PER_LAUNCH tables;
+    fixed-pool and ragged gradients stay in the same call, empty ones are skipped (a table
+    without work is not touched: its step does not advance)."""
+    if len(tables) != len(grads):
+        raise ArgumentError("tables and grads differ in length")
+    if any(g.weights is not None for g in grads):
+        raise ArgumentError("Adam with a weighted gradient: et_sparse_adam takes none")
+    groups: dict = {}
+    for A, g in zip(tables, grads):
+        I = g.indices
+        if isinstance(I, RaggedIndices):
+            if I.nnz == 0 or I.batch == 0:
+                continue
+        elif I.numel() == 0:
+            continue
+        groups.setdefault(A.dtype, []).append(_adam_desc(opt, A, g))
+    flags = (_lib.ET_FLAG_NONTEMPORAL if nontemporal else 0) | (
+        _lib.ET_FLAG_ADAM_ROWWISE if opt.rowwise else 0)
+    L = _lib.load()
+    ncall = 0
+    for dtype, descs in groups.items():
+        for c in range(0, len(descs), _lib.ET_MAX_TABLES_PER_LAUNCH):
+            part = descs[c:c + _lib.ET_MAX_TABLES_PER_LAUNCH]
+            arr = (_lib.AdamDesc * len(part))(*part)
+            nb = ctypes.c_int64(0)
+            _lib.check(L.et_adam_workspace_size(ctypes.addressof(arr), len(part),
+                                                ctypes.byref(nb)))
+            dev = tables[0].device
+            ws = _workspace(nb.value, dev, f"adam{ncall}")
+            _lib.check(L.et_sparse_adam(_lib.TORCH_TO_ET[dtype], ctypes.addressof(arr), len(part),
+                                        opt.eta, opt.beta[0], opt.beta[1], opt.eps, flags,
+                                        ws.data_ptr(), ws.numel(), _lib.stream_handle(dev)))
+            ncall += 1
+
+
 def _update_from_indexer(table, grad: SparseEmbeddingUpdate, indexer: AbstractIndexer,
                          alpha: float, nontemporal: bool, f16_fp32_acc: bool = False):
     if grad.weights is not None:
@@ -1150,8 +1272,9 @@ class PhasedUpdate:
     def update_(self, opt: Descent, stream=None):
         """Phase 2 on ``stream`` (default: the current stream), ordered after the last
         ``index_``.  May be repeated (same indices, new gradient values)."""
-        if isinstance(opt, AdaGrad):
-            raise ArgumentError("PhasedUpdate is SGD-only: AdaGrad has no phased form")
+        if isinstance(opt, (AdaGrad, Adam)):
+            raise ArgumentError(f"PhasedUpdate is SGD-only: {type(opt).__name__} has no phased "
+                                "form")
         if self.device is None:
             return None
         if self._indexed is None:

@@ -1154,6 +1154,114 @@ function update!(opt::SparseAdaGrad, tables::AbstractVector{<:HipTable}, grads::
 end
 
 #####
+##### Sparse Adam (et_sparse_adam; include/embtab.h states the arithmetic).  Lazy: only the
+##### columns a call touches move.  The moments and the step state {beta1^t, beta2^t} live in
+##### the optimiser, per table object; the kernels advance the step themselves.
+#####
+
+const ET_FLAG_ADAM_ROWWISE = UInt32(512)
+
+struct AdamDesc
+    table::Ptr{Cvoid}
+    ld_table::Int64
+    nrows::Int64
+    dim::Int32
+    pool::Int32
+    delta::Ptr{Cvoid}
+    ld_delta::Int64
+    idx::Ptr{Int64}
+    ld_idx::Int64
+    batch::Int64
+    cols_per_page::Int64
+    colptr::Ptr{Int64}
+    nnz::Int64
+    m::Ptr{Cvoid}
+    ld_m::Int64
+    v::Ptr{Cvoid}
+    ld_v::Int64
+    step::Ptr{Cvoid}
+end
+
+mutable struct SparseAdam
+    eta::Float64
+    beta::Tuple{Float64,Float64}
+    eps::Float64
+    rowwise::Bool
+    states::IdDict{Any,Any}
+end
+SparseAdam(eta = 1e-3; beta = (0.9, 0.999), eps = 1e-8, rowwise = false) =
+    SparseAdam(eta, beta, eps, rowwise, IdDict{Any,Any}())
+
+# (m, v, step) of `table`, created on first use (call it before capturing a HIP graph).
+function state(opt::SparseAdam, table::HipTable{S,T}) where {S,T}
+    get!(opt.states, table) do
+        C = _state_eltype(T)
+        vdims = opt.rowwise ? (size(table, 2),) : size(table)
+        (upload(zeros(C, size(table))), upload(zeros(C, vdims)), upload(ones(C, 2)))
+    end
+end
+
+function _adam_desc(opt::SparseAdam, A::HipTable, g::SparseEmbeddingUpdate)
+    u = _update_desc(A, g)
+    m, v, st = state(opt, A)
+    return AdamDesc(u.table, u.ld_table, u.nrows, u.dim, u.pool, u.delta, u.ld_delta, u.idx,
+                    u.ld_idx, u.batch, u.cols_per_page, Ptr{Int64}(C_NULL), 0,
+                    Ptr{Cvoid}(m.ptr), size(A, 1), Ptr{Cvoid}(v.ptr), size(A, 1),
+                    Ptr{Cvoid}(st.ptr))
+end
+
+function _adam_desc(opt::SparseAdam, A::HipTable, g::RaggedEmbeddingUpdate)
+    dp, dld = _ptr_ld(g.delta)
+    tp, ldt, cpp = _device_table(A)
+    R = g.indices
+    m, v, st = state(opt, A)
+    return AdamDesc(tp, ldt, size(A, 2), size(A, 1), 1, dp, dld, R.values.ptr, 1, batchsize(R),
+                    cpp, R.colptr.ptr, length(R.values), Ptr{Cvoid}(m.ptr), size(A, 1),
+                    Ptr{Cvoid}(v.ptr), size(A, 1), Ptr{Cvoid}(st.ptr))
+end
+
+function _sparse_adam(::Type{T}, opt::SparseAdam, descs::Vector{AdamDesc},
+                      nontemporal::Bool) where {T}
+    isempty(descs) && return nothing
+    flags = (nontemporal ? ET_FLAG_NONTEMPORAL : UInt32(0)) |
+            (opt.rowwise ? ET_FLAG_ADAM_ROWWISE : UInt32(0))
+    nb = Ref{Int64}(0)
+    check(ccall((:et_adam_workspace_size, libembtab), Cint,
+                (Ptr{AdamDesc}, Int32, Ref{Int64}), descs, length(descs), nb))
+    ws = _workspace(nb[], -3)
+    check(ccall((:et_sparse_adam, libembtab), Cint,
+                (Cint, Ptr{AdamDesc}, Int32, Float64, Float64, Float64, Float64, UInt32,
+                 Ptr{Cvoid}, Int64, Ptr{Cvoid}),
+                et_dtype(T), descs, length(descs), opt.eta, opt.beta[1], opt.beta[2], opt.eps,
+                flags, ws.ptr, length(ws), stream()))
+    return nothing
+end
+
+function update!(opt::SparseAdam, table::HipTable{S,T}, grad::AdaGradUpdate,
+                 ::Val{Nontemporal} = Val(true)) where {S,T<:UpdateEltype,Nontemporal}
+    isempty(grad.indices) && return nothing
+    return _sparse_adam(T, opt, [_adam_desc(opt, table, grad)], Nontemporal)
+end
+
+# Fixed-pool and ragged gradients stay in one call: one call per element type and at most 32
+# tables (ET_MAX_TABLES_PER_LAUNCH); empty gradients are skipped (their step does not advance).
+function update!(opt::SparseAdam, tables::AbstractVector{<:HipTable}, grads::AbstractVector,
+                 ::Val{Nontemporal} = Val(true)) where {Nontemporal}
+    length(tables) == length(grads) || throw(ArgumentError("tables and grads differ in length"))
+    groups = Dict{DataType,Vector{AdamDesc}}()
+    for (A, g) in zip(tables, grads)
+        g isa WeightedEmbeddingUpdate &&
+            throw(ArgumentError("Adam with a weighted gradient: et_sparse_adam takes none"))
+        isempty(g.indices) && continue
+        push!(get!(groups, eltype(A), AdamDesc[]), _adam_desc(opt, A, g))
+    end
+    for (T, descs) in groups, c in 1:32:length(descs)
+        _sparse_adam(T, opt, descs[c:min(c + 31, length(descs))], Nontemporal)
+    end
+    return nothing
+end
+
+#####
 ##### Sharded Preallocation maplookup over the GPUs of a node (BASELINE config 5):
 ##### one Julia process per GPU, RCCL over xGMI (include/embtab.h, csrc/et_shard.cpp)
 #####

@@ -1111,6 +1111,93 @@ int et_fill_index_uniform(int64_t* idx, int64_t n, int64_t nrows, uint64_t seed,
  * seen by any kernel since the last call. */
 int et_check_errors(uint64_t* oob_count);
 
+/* ---------------------------------------------------------------------------------
+ * Sparse Adam, with an element-wise or a row-wise second moment, over fixed-pool and ragged
+ * gradients (appended under ABI version 9).  Lazy, as torch.optim.SparseAdam: only the
+ * columns a call touches move.  The reference has no optimiser but Descent: this arithmetic
+ * is defined here.
+ *
+ * C is the accumulator type (Float32 for F32 / F16 / BF16 tables, Float64 for F64).  Host
+ * scalars: eta_c, eps_c, b1_c, b2_c are the double arguments rounded to C;
+ * omb1_c = C(1.0 - beta1) and omb2_c = C(1.0 - beta2), the subtraction done in double and
+ * rounded once.  0 <= beta < 1 for both, else ET_ERR_ARG.
+ *
+ *   step state.  `step` is a device array of two C values {p1, p2}, created as {1, 1}: the
+ *   running products beta1^t and beta2^t.  For every table of the call that has work
+ *   (dim > 0, batch > 0, occurrences > 0), once per call and whether or not any index is in
+ *   range: p1' = p1 * b1_c, p2' = p2 * b2_c, one multiply each rounded in C, both written
+ *   back; c1 = 1 - p1', c2 = 1 - p2'.  No pow, no host counter: replaying a captured call
+ *   advances the step exactly as an eager call does.  A table without work is not touched at
+ *   all (table, moments, step).
+ *
+ *   gradient sum g.  et_sparse_adagrad's rule word for word: ET_SGD_CHUNK list positions per
+ *   chunk, g = ((p_0 + p_1) + p_2) + ... in chunk order, a capacity-tail entry adds nothing
+ *   but keeps its position.  A column with no participating occurrence is not written, and
+ *   neither are its moments.
+ *
+ *   element-wise, per feature:
+ *     m' = (b1_c * m) + (omb1_c * g)
+ *     v' = (b2_c * v) + (omb2_c * (g * g))
+ *     mh = m' / c1 ;  vh = v' / c2
+ *     w' = T( C(w) - (eta_c * mh) / (sqrt(vh) + eps_c) )
+ *   row-wise (ET_FLAG_ADAM_ROWWISE; FBGEMM's partial row-wise Adam): m stays element-wise, v
+ *   is one value per column; q = (sum_f g_f^2) / dim evaluated in C (the order of that sum is
+ *   the kernel's choice, as in AdaGrad), v' = (b2_c * v) + (omb2_c * q), then vh, mh and w'
+ *   as above with the scalar vh.
+ *
+ * Every operation is rounded once in C, nothing is contracted, sqrt and / are correctly
+ * rounded, subnormals are kept; the result is rounded to T once (RNE).
+ *
+ * The Float32 vector kernels (16-byte rows, gradients and moments) serve dims up to
+ * ET_ADAM_VEC_MAX_DIM.  No vector kernel uses scratch up to that capacity (171 VGPRs, two
+ * waves per SIMD at 1024; DESIGN.md has the table).  AdaGrad's capacity 2048 is not
+ * instantiated: three streams of eight vectors per lane came to 215 VGPRs in a trial build
+ * (no scratch either), and such a table takes the generic kernels (same results).
+ * ------------------------------------------------------------------------------- */
+#define ET_FLAG_ADAM_ROWWISE 512u /* et_sparse_adam: one second moment per column */
+#define ET_ADAM_VEC_MAX_DIM 1024
+
+/* One table of a sparse Adam update: the fields of et_adagrad_desc up to nnz, same order
+ * and meaning, then the two moments and the step state. */
+typedef struct et_adam_desc {
+    void* table;           /* device pointer, updated in place */
+    int64_t ld_table;
+    int64_t nrows;
+    int32_t dim;
+    int32_t pool;          /* indices per bag of a fixed-pool index; ignored when ragged */
+    const void* delta;     /* dim x batch gradient, column j at delta + j*ld_delta */
+    int64_t ld_delta;
+    const int64_t* idx;    /* fixed pool: the P x B indices; ragged: the values */
+    int64_t ld_idx;        /* fixed pool only */
+    int64_t batch;         /* bags (gradient columns) */
+    int64_t cols_per_page; /* as in et_lookup_desc */
+    const int64_t* colptr; /* NULL: a fixed pool.  Else batch + 1 entries, as et_ragged_desc */
+    int64_t nnz;           /* ragged: capacity of idx */
+    void* m;               /* first moment, type C, dim x nrows, one contiguous allocation */
+    int64_t ld_m;          /* elements between consecutive columns of m (>= dim) */
+    void* v;               /* second moment, type C: dim x nrows, or nrows entries row-wise */
+    int64_t ld_v;          /* as ld_m; ignored by the row-wise form */
+    void* step;            /* two C values {p1, p2}, updated in place */
+} et_adam_desc;
+
+/* Bytes of device workspace et_sparse_adam needs: et_adagrad_workspace_size of the same
+ * sizes. */
+int et_adam_workspace_size(const et_adam_desc* descs, int32_t ntables, int64_t* bytes);
+
+/* Sparse Adam over one or many tables, fixed-pool and ragged ones in one call (semantics
+ * above).  ET_F32 / ET_F64 / ET_F16 / ET_BF16 (anything else: ET_ERR_UNSUPPORTED).  Flags:
+ * ET_FLAG_NONTEMPORAL and ET_FLAG_ADAM_ROWWISE; the SGD's flags return ET_ERR_UNSUPPORTED.
+ * ET_ERR_ARG before any device work: a NULL m / v / step; ld_m < dim, or ld_v < dim
+ * (element-wise); a moment or step block that overlaps a table or another moment or step
+ * block of the call (the two moments may be two blocks of one allocation as long as their
+ * ranges do not overlap); two tables that name the same step; a beta outside [0, 1); and
+ * et_sparse_adagrad's size and table-count rules.  An index outside 1..nrows is counted
+ * (et_check_errors) and writes nothing.  Stream-ordered on the caller's stream only, no
+ * allocation, no host synchronisation: capturable. */
+int et_sparse_adam(int dtype, const et_adam_desc* descs, int32_t ntables, double eta,
+                   double beta1, double beta2, double eps, uint32_t flags, void* workspace,
+                   int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
