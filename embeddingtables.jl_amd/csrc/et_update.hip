@@ -3771,6 +3771,9 @@ extern "C" int et_update_indexed(int dtype, void* table, int64_t ld_table,
 // Sparse Adam (et_sparse_adam): kernels and entry points.
 #include "et_adam.hip"
 
+// Sparse Adam over weighted gradients (et_weighted_adam): pair pass, chunk kernels, entries.
+#include "et_weighted_adam.hip"
+
 // Split sparse SGD over ragged and weighted gradients (et_ragged_sgd_split): kernels, entries.
 #include "et_ragged_sgd_split.hip"
 

@@ -85,6 +85,8 @@ EXPORTS = (
     "et_ragged_sgd_split",
     "et_adam_workspace_size",
     "et_sparse_adam",
+    "et_weighted_adam_workspace_size",
+    "et_weighted_adam",
     "et_quantize_rows",
     "et_quant_maplookup_prealloc",
     "et_fp8_quantize_rows",
@@ -280,6 +282,12 @@ class AdamDesc(ctypes.Structure):
     ]
 
 
+class WeightedAdamDesc(ctypes.Structure):
+    """et_weighted_adam_desc (include/embtab.h): et_adam_desc and the weights."""
+
+    _fields_ = AdamDesc._fields_ + [("weights", ctypes.c_void_p)]
+
+
 class QuantDesc(ctypes.Structure):
     """et_quant_desc (include/embtab.h)."""
 
@@ -374,6 +382,8 @@ def load() -> ctypes.CDLL:
         "et_ragged_sgd_split": ([c_int, vp, i32, dbl, u32, vp, i64, vp], c_int),
         "et_adam_workspace_size": ([vp, i32, vp], c_int),
         "et_sparse_adam": ([c_int, vp, i32, dbl, dbl, dbl, dbl, u32, vp, i64, vp], c_int),
+        "et_weighted_adam_workspace_size": ([vp, i32, vp], c_int),
+        "et_weighted_adam": ([c_int, vp, i32, dbl, dbl, dbl, dbl, u32, vp, i64, vp], c_int),
         "et_quantize_rows": ([vp, i64, i64, i32, i32, vp, i64, vp, vp], c_int),
         "et_quant_maplookup_prealloc": ([c_int, vp, i32, i64, vp, i64, u32, vp], c_int),
         "et_fp8_quantize_rows": ([c_int, vp, i64, i64, i32, vp, i64, vp, vp], c_int),

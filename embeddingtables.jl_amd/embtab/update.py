@@ -269,10 +269,16 @@ class Adam:
     advance it themselves (one multiply per call) and take the bias corrections
     ``c = 1 - beta^t`` from it, so a replayed HIP graph advances the step as an eager call does.
     ``set_state(table, m, v)`` installs caller-owned tensors instead (row blocks of wider ones
-    are fine: unit feature stride, any row stride >= D)."""
+    are fine: unit feature stride, any row stride >= D).
+
+    ``weighted=True`` accepts gradients that carry ``weights`` (the pullback of a weighted or
+    mean-pooled lookup) and sends every gradient of the call through et_weighted_adam: entry
+    ``k`` adds ``weights[k] * delta[bag(k)]`` under the chunk rule of et_weighted_adagrad.  An
+    optimiser built without it refuses such a gradient with ``ArgumentError``, as ever."""
 
     def __init__(self, eta: float = 1e-3, beta=(0.9, 0.999), eps: float = 1e-8,
-                 rowwise: bool = False):
+                 rowwise: bool = False, weighted: bool = False):
+        self.weighted = bool(weighted)
         self.eta = float(eta)
         self.beta = (float(beta[0]), float(beta[1]))
         if not all(0.0 <= b < 1.0 for b in self.beta):
@@ -764,7 +770,8 @@ def update_(*args, nontemporal: bool | None = None, exact: bool | None = None,
     * ``update_(opt::Adam, table, grad)`` and ``update_(opt::Adam, tables, grads)`` — sparse
       Adam (et_sparse_adam), fixed-pool and ragged gradients in the same call, grouped as for
       AdaGrad, with the same keyword rules; a gradient that carries ``weights`` raises
-      ``ArgumentError``.  The moments and the step state are allocated outside the C call, so
+      ``ArgumentError`` unless the optimiser was built with ``Adam(..., weighted=True)``, which
+      sends all its gradients through et_weighted_adam, grouped the same way.  The moments and the step state are allocated outside the C call, so
       they must exist before ``update_`` is captured into a HIP graph: call ``opt.state(A)``
       and ``opt.step(A)`` first, or run one eager step."""
     for a in args[:2]:  # the table(s): first or second argument in every form
@@ -1140,39 +1147,65 @@ def _adam_desc(opt: Adam, table, grad: SparseEmbeddingUpdate) -> _lib.AdamDesc:
                          u.ld_idx, u.batch, u.cols_per_page, None, 0, *tail)
 
 
+def _weighted_adam_desc(opt: Adam, table, grad: SparseEmbeddingUpdate) -> _lib.WeightedAdamDesc:
+    """et_weighted_adam_desc of any gradient: one that carries weights goes to the ragged form
+    through weighted_update_desc (a fixed-pool ``(B, P)`` index gets ``colptr = 1 + P*(0:B)``),
+    the others are their et_adam_desc with NULL weights."""
+    if grad.weights is None:
+        d = _adam_desc(opt, table, grad)
+        return _lib.WeightedAdamDesc(*[getattr(d, f[0]) for f in _lib.AdamDesc._fields_], None)
+    if table.dtype not in _UPDATE_DTYPES:
+        raise NotImplementedError(f"update of a {table.dtype} table")
+    r = grad.ragged()
+    if not r.is_cuda:
+        raise ArgumentError("indices must be in device memory")
+    u = weighted_update_desc(table, grad.delta, r, grad.weights.reshape(-1), None)
+    m, v = opt.state(table)
+    ld = lambda s: int(s.stride(0)) if s.shape[0] > 1 else int(s.shape[1])
+    return _lib.WeightedAdamDesc(u.table, u.ld_table, u.nrows, u.dim, 1, u.delta, u.ld_delta,
+                                 u.idx, 1, u.batch, u.cols_per_page, u.colptr, u.nnz,
+                                 m.data_ptr(), ld(m), v.data_ptr(), 1 if opt.rowwise else ld(v),
+                                 opt.step(table).data_ptr(), u.weights)
+
+
 def _update_adam(opt: Adam, tables, grads, nontemporal: bool):
     """One et_sparse_adam call per element type and at most ET_MAX_TABLES_PER_LAUNCH tables;
     fixed-pool and ragged gradients stay in the same call, empty ones are skipped (a table
-    without work is not touched: its step does not advance)."""
+    without work is not touched: its step does not advance).  An optimiser built with
+    ``weighted=True`` makes the same calls to et_weighted_adam, which also takes gradients that
+    carry weights; otherwise those are refused, as ever."""
     if len(tables) != len(grads):
         raise ArgumentError("tables and grads differ in length")
-    if any(g.weights is not None for g in grads):
+    if not opt.weighted and any(g.weights is not None for g in grads):
         raise ArgumentError("Adam with a weighted gradient: et_sparse_adam takes none")
+    desc_of = _weighted_adam_desc if opt.weighted else _adam_desc
     groups: dict = {}
     for A, g in zip(tables, grads):
-        I = g.indices
+        I = g.ragged() if g.weights is not None else g.indices
         if isinstance(I, RaggedIndices):
             if I.nnz == 0 or I.batch == 0:
                 continue
         elif I.numel() == 0:
             continue
-        groups.setdefault(A.dtype, []).append(_adam_desc(opt, A, g))
+        groups.setdefault(A.dtype, []).append(desc_of(opt, A, g))
     flags = (_lib.ET_FLAG_NONTEMPORAL if nontemporal else 0) | (
         _lib.ET_FLAG_ADAM_ROWWISE if opt.rowwise else 0)
     L = _lib.load()
+    Desc, size, run, key = ((_lib.WeightedAdamDesc, L.et_weighted_adam_workspace_size,
+                             L.et_weighted_adam, "weighted_adam") if opt.weighted else
+                            (_lib.AdamDesc, L.et_adam_workspace_size, L.et_sparse_adam, "adam"))
     ncall = 0
     for dtype, descs in groups.items():
         for c in range(0, len(descs), _lib.ET_MAX_TABLES_PER_LAUNCH):
             part = descs[c:c + _lib.ET_MAX_TABLES_PER_LAUNCH]
-            arr = (_lib.AdamDesc * len(part))(*part)
+            arr = (Desc * len(part))(*part)
             nb = ctypes.c_int64(0)
-            _lib.check(L.et_adam_workspace_size(ctypes.addressof(arr), len(part),
-                                                ctypes.byref(nb)))
+            _lib.check(size(ctypes.addressof(arr), len(part), ctypes.byref(nb)))
             dev = tables[0].device
-            ws = _workspace(nb.value, dev, f"adam{ncall}")
-            _lib.check(L.et_sparse_adam(_lib.TORCH_TO_ET[dtype], ctypes.addressof(arr), len(part),
-                                        opt.eta, opt.beta[0], opt.beta[1], opt.eps, flags,
-                                        ws.data_ptr(), ws.numel(), _lib.stream_handle(dev)))
+            ws = _workspace(nb.value, dev, f"{key}{ncall}")
+            _lib.check(run(_lib.TORCH_TO_ET[dtype], ctypes.addressof(arr), len(part), opt.eta,
+                           opt.beta[0], opt.beta[1], opt.eps, flags, ws.data_ptr(), ws.numel(),
+                           _lib.stream_handle(dev)))
             ncall += 1
 
 

@@ -1187,10 +1187,11 @@ mutable struct SparseAdam
     beta::Tuple{Float64,Float64}
     eps::Float64
     rowwise::Bool
+    weighted::Bool  # take gradients that carry weights, through et_weighted_adam
     states::IdDict{Any,Any}
 end
-SparseAdam(eta = 1e-3; beta = (0.9, 0.999), eps = 1e-8, rowwise = false) =
-    SparseAdam(eta, beta, eps, rowwise, IdDict{Any,Any}())
+SparseAdam(eta = 1e-3; beta = (0.9, 0.999), eps = 1e-8, rowwise = false, weighted = false) =
+    SparseAdam(eta, beta, eps, rowwise, weighted, IdDict{Any,Any}())
 
 # (m, v, step) of `table`, created on first use (call it before capturing a HIP graph).
 function state(opt::SparseAdam, table::HipTable{S,T}) where {S,T}
@@ -1243,20 +1244,98 @@ function update!(opt::SparseAdam, table::HipTable{S,T}, grad::AdaGradUpdate,
     return _sparse_adam(T, opt, [_adam_desc(opt, table, grad)], Nontemporal)
 end
 
+# Adam over a weighted gradient (et_weighted_adam; include/embtab.h "Sparse Adam over weighted
+# gradients"): et_adam_desc and the weights.  An optimiser built with `weighted = true` sends
+# every gradient through it (NULL weights: et_sparse_adam's behaviour).
+struct WeightedAdamDesc
+    table::Ptr{Cvoid}
+    ld_table::Int64
+    nrows::Int64
+    dim::Int32
+    pool::Int32
+    delta::Ptr{Cvoid}
+    ld_delta::Int64
+    idx::Ptr{Int64}
+    ld_idx::Int64
+    batch::Int64
+    cols_per_page::Int64
+    colptr::Ptr{Int64}
+    nnz::Int64
+    m::Ptr{Cvoid}
+    ld_m::Int64
+    v::Ptr{Cvoid}
+    ld_v::Int64
+    step::Ptr{Cvoid}
+    weights::Ptr{Cvoid}
+end
+
+function _weighted_adam_desc(opt::SparseAdam, A::HipTable, g::AdaGradUpdate)
+    d = _adam_desc(opt, A, g)
+    return WeightedAdamDesc(d.table, d.ld_table, d.nrows, d.dim, d.pool, d.delta, d.ld_delta,
+                            d.idx, d.ld_idx, d.batch, d.cols_per_page, d.colptr, d.nnz, d.m,
+                            d.ld_m, d.v, d.ld_v, d.step, Ptr{Cvoid}(C_NULL))
+end
+
+function _weighted_adam_desc(opt::SparseAdam, A::HipTable{S,T},
+                             g::WeightedEmbeddingUpdate) where {S,T}
+    dp, dld = _ptr_ld(g.delta)
+    tp, ldt, cpp = _device_table(A)
+    R = g.indices
+    m, v, st = state(opt, A)
+    return WeightedAdamDesc(tp, ldt, size(A, 2), size(A, 1), 1, dp, dld, R.values.ptr, 1,
+                            batchsize(R), cpp, R.colptr.ptr, length(R.values), Ptr{Cvoid}(m.ptr),
+                            size(A, 1), Ptr{Cvoid}(v.ptr), size(A, 1), Ptr{Cvoid}(st.ptr),
+                            _weights_ptr(T, g.weights))
+end
+
+function _weighted_adam(::Type{T}, opt::SparseAdam, descs::Vector{WeightedAdamDesc},
+                        nontemporal::Bool) where {T}
+    isempty(descs) && return nothing
+    flags = (nontemporal ? ET_FLAG_NONTEMPORAL : UInt32(0)) |
+            (opt.rowwise ? ET_FLAG_ADAM_ROWWISE : UInt32(0))
+    nb = Ref{Int64}(0)
+    check(ccall((:et_weighted_adam_workspace_size, libembtab), Cint,
+                (Ptr{WeightedAdamDesc}, Int32, Ref{Int64}), descs, length(descs), nb))
+    ws = _workspace(nb[], -3)
+    check(ccall((:et_weighted_adam, libembtab), Cint,
+                (Cint, Ptr{WeightedAdamDesc}, Int32, Float64, Float64, Float64, Float64, UInt32,
+                 Ptr{Cvoid}, Int64, Ptr{Cvoid}),
+                et_dtype(T), descs, length(descs), opt.eta, opt.beta[1], opt.beta[2], opt.eps,
+                flags, ws.ptr, length(ws), stream()))
+    return nothing
+end
+
+function update!(opt::SparseAdam, table::HipTable{S,T}, grad::WeightedEmbeddingUpdate,
+                 ::Val{Nontemporal} = Val(true)) where {S,T<:UpdateEltype,Nontemporal}
+    opt.weighted ||
+        throw(ArgumentError("Adam with a weighted gradient: et_sparse_adam takes none"))
+    isempty(grad.indices) && return nothing
+    return _weighted_adam(T, opt, [_weighted_adam_desc(opt, table, grad)], Nontemporal)
+end
+
 # Fixed-pool and ragged gradients stay in one call: one call per element type and at most 32
 # tables (ET_MAX_TABLES_PER_LAUNCH); empty gradients are skipped (their step does not advance).
+# With `weighted = true` the same calls go to et_weighted_adam, weighted gradients included.
 function update!(opt::SparseAdam, tables::AbstractVector{<:HipTable}, grads::AbstractVector,
                  ::Val{Nontemporal} = Val(true)) where {Nontemporal}
     length(tables) == length(grads) || throw(ArgumentError("tables and grads differ in length"))
     groups = Dict{DataType,Vector{AdamDesc}}()
+    wgroups = Dict{DataType,Vector{WeightedAdamDesc}}()
     for (A, g) in zip(tables, grads)
-        g isa WeightedEmbeddingUpdate &&
+        g isa WeightedEmbeddingUpdate && !opt.weighted &&
             throw(ArgumentError("Adam with a weighted gradient: et_sparse_adam takes none"))
         isempty(g.indices) && continue
-        push!(get!(groups, eltype(A), AdamDesc[]), _adam_desc(opt, A, g))
+        if opt.weighted
+            push!(get!(wgroups, eltype(A), WeightedAdamDesc[]), _weighted_adam_desc(opt, A, g))
+        else
+            push!(get!(groups, eltype(A), AdamDesc[]), _adam_desc(opt, A, g))
+        end
     end
     for (T, descs) in groups, c in 1:32:length(descs)
         _sparse_adam(T, opt, descs[c:min(c + 31, length(descs))], Nontemporal)
+    end
+    for (T, descs) in wgroups, c in 1:32:length(descs)
+        _weighted_adam(T, opt, descs[c:min(c + 31, length(descs))], Nontemporal)
     end
     return nothing
 end

@@ -1198,6 +1198,85 @@ int et_sparse_adam(int dtype, const et_adam_desc* descs, int32_t ntables, double
                    double beta1, double beta2, double eps, uint32_t flags, void* workspace,
                    int64_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Sparse Adam over weighted gradients: the pullback of a weighted or mean-pooled lookup
+ * (appended under ABI version 9).  Everything of et_sparse_adam above holds word for word: the
+ * step state, m', v' (element-wise and ET_FLAG_ADAM_ROWWISE), w', the laziness, "a table without
+ * work is not touched", every operation rounded once in C.  Only the gradient sum g of a table
+ * that carries weights differs, and it is et_weighted_adagrad's rule word for word: the
+ * column's list in increasing k, cut into chunks of ET_SGD_CHUNK list positions; every chunk
+ * starts from p_c = +0; for every entry of the chunk that a bag covers, in order,
+ * t = C(w_k) * C(delta[:, bag(k)]); p_c = p_c + t (two roundings, never an fma);
+ * g = ((p_0 + p_1) + p_2) + ... in chunk order.  An entry no bag covers adds nothing, keeps its
+ * list position, and its weight is never read (it need not be a valid number).  A column
+ * participates whatever the weight: a weight of 0 still writes the column and both moments and
+ * advances the step.
+ *
+ * A weighted table is in the ragged form (idx, colptr, the capacity nnz, as et_ragged_desc);
+ * `weights` has nnz entries of type C and entry k of idx pairs with weights[k].
+ *
+ * How the weights reach the kernels: one pass over the sorted occurrence list writes a pair
+ * stream into the workspace, pairs[i] = (bag, weight) of list position i, with weight 1.0 for
+ * an entry no bag covers and for every entry of a table without weights.  C = Float32: one
+ * 8-byte word (bag, bits of the weight).  C = Float64: one 16-byte record (bag, 0, weight).
+ * If any table of the call carries weights, all tables of the call are summed from the pair
+ * stream; x * 1.0 is x for every x that is not a NaN (signed zeros and subnormals included),
+ * and a NaN stays a NaN in its position (which NaN is not pinned).  If none does, the call
+ * runs et_sparse_adam's own kernels.
+ *
+ * Workspace layout: the et_adam_workspace_size bytes of the same sizes first, laid out as
+ * et_sparse_adam lays them out, then the pair stream at the next 256-byte boundary:
+ *   et_weighted_adam_workspace_size = et_adam_workspace_size + roundup(16 * n, 256)
+ * with n the occurrences of all tables with work (nnz of a ragged table, pool * batch of a
+ * fixed-pool one); 16 bytes per occurrence whatever C is.
+ *
+ * Consequences (tests/test_gpu_weighted_adam.py pins them):
+ *   (a) with every covered weight 1.0 the table, m, v and step equal et_sparse_adam on the
+ *       same ragged index, bit for bit, element-wise and row-wise;
+ *   (b) for ET_F32 / ET_F64 the result equals et_sparse_adam of the expanded gradient
+ *       E[:, k] = fl_C(w_k * delta[:, bag(k)]) with every covered entry its own bag;
+ *   (c) mean mode needs no entry of its own: its gradient carries w_k = 1 / len(bag(k)).
+ * ------------------------------------------------------------------------------- */
+
+/* One table of a weighted Adam update: the fields of et_adam_desc, same order and meaning,
+ * and the weights. */
+typedef struct et_weighted_adam_desc {
+    void* table;           /* device pointer, updated in place */
+    int64_t ld_table;
+    int64_t nrows;
+    int32_t dim;
+    int32_t pool;          /* fixed pool (weights == NULL only); ignored when ragged */
+    const void* delta;     /* dim x batch gradient, column j at delta + j*ld_delta */
+    int64_t ld_delta;
+    const int64_t* idx;    /* fixed pool: the P x B indices; ragged: the values */
+    int64_t ld_idx;        /* fixed pool only */
+    int64_t batch;         /* bags (gradient columns) */
+    int64_t cols_per_page; /* as in et_lookup_desc */
+    const int64_t* colptr; /* NULL: a fixed pool.  Else batch + 1 entries, as et_ragged_desc */
+    int64_t nnz;           /* ragged: capacity of idx and of weights */
+    void* m;               /* as in et_adam_desc */
+    int64_t ld_m;
+    void* v;               /* as in et_adam_desc */
+    int64_t ld_v;
+    void* step;            /* as in et_adam_desc */
+    const void* weights;   /* type C, nnz entries, or NULL */
+} et_weighted_adam_desc;
+
+/* Bytes of device workspace et_weighted_adam needs (the layout formula above). */
+int et_weighted_adam_workspace_size(const et_weighted_adam_desc* descs, int32_t ntables,
+                                    int64_t* bytes);
+
+/* Sparse Adam over gradients with a weight per entry (semantics above).  A table with
+ * weights == NULL behaves exactly as in et_sparse_adam, fixed-pool or ragged; one call may
+ * mix all three kinds.  weights != NULL with colptr == NULL is ET_ERR_ARG, and so are weights
+ * not aligned to C, and weights that overlap a table, moment or step block of the call.  Every
+ * other check and flag rule is et_sparse_adam's, reported before any device work.
+ * Stream-ordered on the caller's stream only, no allocation, no host synchronisation; every
+ * node of a captured call is a kernel. */
+int et_weighted_adam(int dtype, const et_weighted_adam_desc* descs, int32_t ntables, double eta,
+                     double beta1, double beta2, double eps, uint32_t flags, void* workspace,
+                     int64_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
