@@ -269,6 +269,8 @@ extern "C" int et_split_slabs(int dtype, const void* src, int64_t ld_src, int64_
                                const_cast<void*>(src), ld_src, stream);
 }
 
+#include "et_interact.hip"
+
 ET_OOB_READER(misc)
 
 extern "C" int et_check_errors(uint64_t* oob_count) {

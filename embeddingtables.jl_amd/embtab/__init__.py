@@ -14,6 +14,7 @@ from .tables import (AbstractEmbeddingTable, AbstractLookupType, ArgumentError, 
 from .ragged import RaggedIndices
 from .quant import QuantizedEmbedding
 from .weighted import WeightedIndices
+from .interact import interact, interact_
 from .lookup import (AbstractExecutionStrategy, DefaultStrategy, NoTangent,
                      PreallocationPlan, PreallocationStrategy, SimpleParallelStrategy, colwrap, destination, lookup,
                      lookup_, maplookup, maplookup_)
@@ -33,4 +34,5 @@ __all__ = [
     "IndexerView", "index_", "gettranslations", "update_", "optimise_update_",
     "ensemble_update", "PhasedUpdate", "EmbtabError", "check_errors",
     "RaggedIndices", "AdaGrad", "QuantizedEmbedding", "WeightedIndices", "Adam",
+    "interact", "interact_",
 ]

@@ -34,6 +34,10 @@ ET_FLAG_SGD_HOT_PASS = 128
 ET_FLAG_ADAGRAD_ROWWISE = 512
 ET_FLAG_ADAM_ROWWISE = 512  # the same bit: one row-wise flag per optimiser family
 ET_ADAM_VEC_MAX_DIM = 1024
+ET_FLAG_INTERACT_ITSELF = 1024
+ET_INTERACT_MAX_VECTORS, ET_INTERACT_MAX_DIM = 32, 1024
+# include/embtab.h: the interaction grid is at most GRID_CAP workgroups of WAVES samples
+ET_INTERACT_WAVES, ET_INTERACT_GRID_CAP = 4, 2048
 ET_POOL_SUM, ET_POOL_MEAN = 0, 1
 ET_QUANT_INT, ET_FP8_E4M3, ET_FP8_E5M2, ET_QUANT_MXFP4 = 0, 1, 2, 3  # a quantised launch group
 ET_MAX_TABLES_PER_LAUNCH = 32
@@ -94,6 +98,8 @@ EXPORTS = (
     "et_mx4_quantize_rows",
     "et_mx4_maplookup_prealloc",
     "et_quant_weighted_maplookup_prealloc",
+    "et_interact",
+    "et_interact_backward",
     "et_concat_slabs",
     "et_split_slabs",
     "et_push_cols",
@@ -392,6 +398,9 @@ def load() -> ctypes.CDLL:
         "et_mx4_maplookup_prealloc": ([c_int, vp, i32, i64, vp, i64, u32, vp], c_int),
         "et_quant_weighted_maplookup_prealloc": ([c_int, c_int, vp, i32, i64, vp, i64, u32, vp],
                                                  c_int),
+        "et_interact": ([c_int, vp, i64, i64, i32, i32, i32, vp, i64, u32, vp], c_int),
+        "et_interact_backward": ([c_int, vp, i64, vp, i64, i64, i32, i32, i32, vp, i64, u32, vp],
+                                 c_int),
         "et_concat_slabs": ([c_int, vp, i32, i64, i64, vp, vp, vp, i64, vp], c_int),
         "et_split_slabs": ([c_int, vp, i64, i64, i32, vp, vp, vp, i64, vp], c_int),
         "et_push_cols": ([c_int, vp, i64, i64, i64, i64, vp, i32, vp], c_int),

@@ -20,6 +20,7 @@ import weakref
 import torch
 
 from . import _lib
+from .interact import interact, interact_backward
 from .lookup import (NoTangent, PreallocationStrategy, AbstractExecutionStrategy, colwrap,
                      lookup, maplookup, _ld, _check_idx)
 from .quant import refuse as refuse_quantized
@@ -106,7 +107,16 @@ def uncompress(x: SparseEmbeddingUpdate, dstcols: int | None = None,
 
 def rrule(f, *args):
     """``ChainRulesCore.rrule`` for ``lookup`` and ``maplookup``: returns
-    ``(y, pullback)``; the pullback returns ``SparseEmbeddingUpdate``s."""
+    ``(y, pullback)``; the pullback returns ``SparseEmbeddingUpdate``s.  For ``interact`` the
+    pullback returns the dense ``dX`` (one et_interact_backward launch)."""
+    if f is interact:
+        X, rest = args[0], args[1:]
+        y = interact(X, *rest)
+
+        def interact_pullback(dY):
+            return (NoTangent(), interact_backward(X, dY, *rest)) + (NoTangent(),) * len(rest)
+
+        return y, interact_pullback
     if f is lookup:
         A, I = args
         refuse_quantized(A, "rrule")

@@ -1439,9 +1439,57 @@ function maplookup!(S::ShardedPreallocation, dst::HipMatrix{T}, tables::Vector{<
     return dst
 end
 
+#####
+##### Pairwise dot interaction (include/embtab.h, "Pairwise dot interaction")
+#####
+
+const ET_FLAG_INTERACT_ITSELF = UInt32(1024)
+
+_interact_np(F, itself) = itself ? F * (F + 1) ÷ 2 : F * (F - 1) ÷ 2
+
+# X is the (F*dim) x B matrix of maplookup(PreallocationStrategy(dim), ...): Y is
+# (copy + NP) x B, its first `copy` rows those of X, then the strict lower triangle of every
+# sample's F x F dot products (the diagonal too with `itself`).
+function interact!(Y::HipMatrix{T}, X::HipMatrix{T}, dim::Integer; copy::Integer = dim,
+                   itself::Bool = false) where {T<:Union{Float32,Float16}}
+    size(X, 1) % dim == 0 || throw(ArgumentError("size(X, 1) is no multiple of dim"))
+    F = size(X, 1) ÷ dim
+    size(Y) == (copy + _interact_np(F, itself), size(X, 2)) || throw(ArgumentError("size of Y"))
+    flags = ET_FLAG_NONTEMPORAL | (itself ? ET_FLAG_INTERACT_ITSELF : UInt32(0))
+    check(ccall((:et_interact, libembtab), Cint,
+                (Cint, Ptr{Cvoid}, Int64, Int64, Int32, Int32, Int32, Ptr{Cvoid}, Int64, UInt32,
+                 Ptr{Cvoid}),
+                et_dtype(T), X.ptr, leading(X), size(X, 2), F, dim, copy, Y.ptr, leading(Y), flags,
+                stream()))
+    return Y
+end
+
+function interact(X::HipMatrix{T}, dim::Integer; copy::Integer = dim, itself::Bool = false) where {T}
+    F = size(X, 1) ÷ dim
+    return interact!(HipArray{T}(undef, copy + _interact_np(F, itself), size(X, 2)), X, dim;
+                     copy = copy, itself = itself)
+end
+
+# dX of interact at X for the output gradient dY: a fresh matrix of X's size.  Its first
+# `dim` rows are the dense network's gradient; the rest goes to the tables' pullback.
+function interact_pullback(X::HipMatrix{T}, dY::HipMatrix{T}, dim::Integer; copy::Integer = dim,
+                           itself::Bool = false) where {T<:Union{Float32,Float16}}
+    F = size(X, 1) ÷ dim
+    size(dY) == (copy + _interact_np(F, itself), size(X, 2)) || throw(ArgumentError("size of dY"))
+    dX = HipArray{T}(undef, size(X, 1), size(X, 2))
+    flags = ET_FLAG_NONTEMPORAL | (itself ? ET_FLAG_INTERACT_ITSELF : UInt32(0))
+    check(ccall((:et_interact_backward, libembtab), Cint,
+                (Cint, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Int64, Int64, Int32, Int32, Int32, Ptr{Cvoid},
+                 Int64, UInt32, Ptr{Cvoid}),
+                et_dtype(T), X.ptr, leading(X), dY.ptr, leading(dY), size(X, 2), F, dim, copy,
+                dX.ptr, leading(dX), flags, stream()))
+    return dX
+end
+
 export QuantizedEmbedding, HipEmbedding, HipSplitEmbedding, HipArray, HipVector, HipMatrix, EmbtabError,
     DeviceColumns, HipIndexer, ShardedPreallocation, shard_plan, comm_id, comm_init,
     comm_destroy, comm_loopback, RaggedIndices, RaggedEmbeddingUpdate, bag_ids,
-    WeightedIndices, WeightedEmbeddingUpdate, weight_grad, arithmetic_colptr
+    WeightedIndices, WeightedEmbeddingUpdate, weight_grad, arithmetic_colptr, interact, interact!,
+    interact_pullback
 
 end # module

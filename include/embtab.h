@@ -1277,6 +1277,62 @@ int et_weighted_adam(int dtype, const et_weighted_adam_desc* descs, int32_t ntab
                      double beta1, double beta2, double eps, uint32_t flags, void* workspace,
                      int64_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------
+ * Pairwise dot interaction (DLRM's interaction layer), forward and backward, on the matrix
+ * units.  The reference stops at the concatenated maplookup(PreallocationStrategy) matrix;
+ * the definitions here are the contract.
+ *
+ * X is a (B, F*D) view with unit column stride and row stride ld_x >= F*D: in the reference's
+ * terms the column-major (k + sum D) x B matrix of maplookup(PreallocationStrategy(D), ...),
+ * all tables of one D and the dense vector in the prepended rows.  T is ET_F32, ET_F16 or
+ * ET_BF16.  Vector f of sample b is x_f = X[b, f*D : (f+1)*D];  F = nvec, D = dim, c = copy.
+ *
+ * Forward, into Y of shape (B, c + NP), row stride ld_y >= c + NP:
+ *   Y[b, 0:c] = X[b, 0:c]                          (a bit copy; 0 <= c <= F*D; DLRM uses c = D)
+ *   Y[b, c + p(i,j)] = O(sum_k x_i[k] * x_j[k])    for 0 <= j < i < F,
+ *                                                  p(i,j) = i(i-1)/2 + j,  NP = F(F-1)/2
+ *   with ET_FLAG_INTERACT_ITSELF the diagonal is included: j <= i, p(i,j) = i(i+1)/2 + j,
+ *   NP = F(F+1)/2.
+ *   Products and sums are Float32 as the matrix instruction forms them (v_mfma_f32_32x32x2_f32,
+ *   v_mfma_f32_32x32x16_f16 / _bf16); O is one RNE conversion to T.  The order of the sum over
+ *   k is the instruction's and the kernel's K schedule; it is fixed per (T, F, D): a sample's
+ *   output bits depend neither on B nor on where the sample sits in the batch, nor on the
+ *   call (no atomics, nothing is summed across waves).  Subnormal operands and results are
+ *   treated as the matrix instruction treats them.
+ *
+ * Backward, from X and dY (row stride ld_dy >= c + NP) into dX of shape (B, F*D), row stride
+ * ld_dx >= F*D:
+ *   G = the symmetric fill of the triangle part of dY: G[i,j] = G[j,i] = dY[b, c + p(max, min)],
+ *       G[i,i] = 0 without ET_FLAG_INTERACT_ITSELF
+ *   dx_i = sum_{j != i} G[i,j] * x_j   (+ 2 * G[i,i] * x_i with ET_FLAG_INTERACT_ITSELF)
+ *   then dX[b, 0:c] += dY[b, 0:c];  Float32 accumulation, one RNE conversion to T.
+ *
+ * Limits: 1 <= F <= ET_INTERACT_MAX_VECTORS (one 32x32 tile per sample), D * sizeof(T) a
+ * multiple of 16 (the vector-row rule), D <= ET_INTERACT_MAX_DIM; anything else, every other
+ * dtype and every other flag return ET_ERR_UNSUPPORTED before any launch, and so do rows of X
+ * or dX that are not 16-byte aligned (the pointer and ld * sizeof(T)); Y and dY need only the
+ * alignment of T.  ET_ERR_ARG: a negative batch, copy outside 0..F*D, a NULL pointer, a row
+ * stride below the row, Y or dX overlapping X or dY.  batch == 0 is a successful no-op.
+ * No workspace, no host synchronisation, stream-ordered on the caller's stream: capturable.
+ * The kernels never read an element of a row beyond F*D (c + NP for dY) and never write
+ * beyond the same extents.  ET_FLAG_NONTEMPORAL applies to the stores of Y and dX.
+ *
+ * The grid is capped: ET_INTERACT_GRID_CAP workgroups of ET_INTERACT_WAVES waves, a wave per
+ * sample, striding over the batch.
+ * ------------------------------------------------------------------------------- */
+#define ET_FLAG_INTERACT_ITSELF 1024u /* et_interact*: the diagonal x_i . x_i is part of Y */
+#define ET_INTERACT_MAX_VECTORS 32
+#define ET_INTERACT_MAX_DIM 1024
+#define ET_INTERACT_WAVES 4
+#define ET_INTERACT_GRID_CAP 2048
+
+int et_interact(int dtype, const void* x, int64_t ld_x, int64_t batch, int32_t nvec, int32_t dim,
+                int32_t copy, void* y, int64_t ld_y, uint32_t flags, void* stream);
+
+int et_interact_backward(int dtype, const void* x, int64_t ld_x, const void* dy, int64_t ld_dy,
+                         int64_t batch, int32_t nvec, int32_t dim, int32_t copy, void* dx,
+                         int64_t ld_dx, uint32_t flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
