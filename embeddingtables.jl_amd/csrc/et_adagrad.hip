@@ -379,7 +379,9 @@ __device__ __forceinline__ void ada_apply_generic(T* __restrict__ w, C* __restri
         if (lane == 0) store_scalar<NT>(sp, s2);
 }
 
-template <typename T, typename C, bool ROW, bool NT>
+// G is the gradient's element type: the table's, or Float16 / BFloat16 for a Float32 table
+// updated from a 16-bit gradient (one converted load per feature).
+template <typename T, typename C, bool ROW, bool NT, typename G = T>
 __global__ __launch_bounds__(256) void k_adagrad_chunks_generic(
     UpdatePack pack, AdaPack ap, int ntables, const uint32_t* __restrict__ vals,
     const ChunkRec* __restrict__ recs, const uint32_t* __restrict__ counters,
@@ -395,7 +397,7 @@ __global__ __launch_bounds__(256) void k_adagrad_chunks_generic(
         if ((pack.vec_mask >> t) & 1u) continue;  // the vector kernels' table
         const et_update_desc& d = pack.d[t];
         const int dim = d.dim;
-        const T* __restrict__ delta = reinterpret_cast<const T*>(d.delta);
+        const G* __restrict__ delta = reinterpret_cast<const G*>(d.delta);
         const uint64_t ldd = (uint64_t)d.ld_delta;
         const bool ragged = (ap.ragged >> t) & 1u;
         const uint32_t occ_off = pack.occ_off[t], pool = (uint32_t)d.pool;
@@ -414,7 +416,7 @@ __global__ __launch_bounds__(256) void k_adagrad_chunks_generic(
 #pragma unroll
                     for (int j = 0; j < kAdaE; ++j)
                         b[j] = (uint32_t)__shfl((int)myb, (int)(j0 + j), 64);
-                    T x[kAdaE][kAdaK];
+                    G x[kAdaE][kAdaK];
 #pragma unroll
                     for (int j = 0; j < kAdaE; ++j)
 #pragma unroll
@@ -422,7 +424,7 @@ __global__ __launch_bounds__(256) void k_adagrad_chunks_generic(
                             const int f = f0 + lane + 64 * k;
                             x[j][k] = b[j] != 0u && f < dim
                                           ? delta[(uint64_t)(b[j] - 1u) * ldd + f]
-                                          : T(0);
+                                          : G(0);
                         }
 #pragma unroll
                     for (int j = 0; j < kAdaE; ++j) {
@@ -607,18 +609,32 @@ inline int validate_adagrad(int dtype, const et_adagrad_desc* descs, int ntables
 }
 
 constexpr uint32_t kAdaFlags = ET_FLAG_NONTEMPORAL | ET_FLAG_ADAGRAD_ROWWISE;
+// a Float32 table's 16-bit gradient: et_sparse_adagrad and et_sparse_adam only
+constexpr uint32_t kDeltaFlags = ET_FLAG_DELTA_F16 | ET_FLAG_DELTA_BF16;
 constexpr uint32_t kAdaSgdOnly = ET_FLAG_F16_FP32_ACC | ET_FLAG_EXACT_UPDATE | ET_FLAG_SGD_UNFUSED |
                                  ET_FLAG_SGD_F64_ALPHA | ET_FLAG_SGD_INDEX_ONLY |
                                  ET_FLAG_SGD_APPLY_ONLY | ET_FLAG_SGD_HOT_PASS |
                                  ET_FLAG_EXACT_IF_FAST;
 
-inline int check_adagrad_call(int dtype, uint32_t flags) {
+// The gradient-type flags of an entry that takes them.
+inline int check_delta_flags(const char* who, int dtype, uint32_t flags) {
+    if ((flags & kDeltaFlags) == kDeltaFlags)
+        return fail(ET_ERR_ARG, "%s: a Float16 and a BFloat16 gradient flag together", who);
+    if ((flags & kDeltaFlags) && dtype != ET_F32)
+        return fail(ET_ERR_UNSUPPORTED, "%s: a 16-bit gradient needs a Float32 table (dtype %d)",
+                    who, dtype);
+    return ET_OK;
+}
+
+// `known`: flags beyond kAdaFlags this entry takes (kDeltaFlags for et_sparse_adagrad).
+inline int check_adagrad_call(int dtype, uint32_t flags, uint32_t known = 0) {
     if (dtype != ET_F32 && dtype != ET_F64 && dtype != ET_F16 && dtype != ET_BF16)
         return fail(ET_ERR_UNSUPPORTED, "sparse AdaGrad: dtype %d", dtype);
     if (flags & kAdaSgdOnly)
         return fail(ET_ERR_UNSUPPORTED, "sparse AdaGrad: flags 0x%x belong to the SGD", flags & kAdaSgdOnly);
-    if (flags & ~kAdaFlags) return fail(ET_ERR_ARG, "sparse AdaGrad: unknown flags 0x%x", flags & ~kAdaFlags);
-    return ET_OK;
+    if (flags & ~(kAdaFlags | known))
+        return fail(ET_ERR_ARG, "sparse AdaGrad: unknown flags 0x%x", flags & ~(kAdaFlags | known));
+    return check_delta_flags("sparse AdaGrad", dtype, flags & known);
 }
 
 // f(Elem<T, C>{}, std::bool_constant<ROW>{}, std::bool_constant<NT>{})
@@ -646,6 +662,7 @@ struct AdaRun {
     AdaWs w;
     Grouped gr;
     VecGroups vg;
+    VecGroups vg8;  // 16-bit gradients: the same tables by the capacity of the 8-feature layout
     int ntables, pdim;
     int64_t n;
     uint32_t sent;
@@ -699,6 +716,7 @@ struct AdaFrontOpts {
     uint32_t no_vec = 0;
     int vec_max_dim = 2048;
     bool kernel_clears = false;
+    bool delta16 = false;  // the gradients are Float16 / BFloat16 (et_mixed_grad.hip)
 };
 
 __global__ __launch_bounds__(256) void k_clear_u32(uint32_t* __restrict__ p, int64_t n) {
@@ -756,16 +774,20 @@ inline int pack_adagrad_tables(int dtype, const et_adagrad_desc* descs, int ntab
             if (a.batch > max_batch) max_batch = a.batch;
         }
         // the vector kernels: Float32 rows, gradient rows and state rows of 16-byte multiples
+        // (16 bytes of a 16-bit gradient are 8 features: dim and ld_delta in multiples of 8)
+        const int gv = fo.delta16 ? 8 : 4;
         const bool vec = dtype == ET_F32 && (a.cols_per_page > 0 || aligned16(a.table)) &&
-                         a.ld_table % 4 == 0 && a.dim % 4 == 0 && a.dim <= fo.vec_max_dim &&
+                         a.ld_table % 4 == 0 && a.dim % gv == 0 && a.dim <= fo.vec_max_dim &&
                          !((fo.no_vec >> t) & 1u) &&
-                         aligned16(a.delta) && a.ld_delta % 4 == 0 &&
+                         aligned16(a.delta) && a.ld_delta % gv == 0 &&
                          (rowwise ? ((uintptr_t)a.state & 3u) == 0
                                   : aligned16(a.state) && a.ld_state % 4 == 0);
-        if (vec && run.vg.add(vec_dim_ok(a.dim) ? a.dim : masked_capacity(a.dim), t))
+        if (vec && run.vg.add(vec_dim_ok(a.dim) ? a.dim : masked_capacity(a.dim), t)) {
             pack.vec_mask |= 1u << t;
-        else
+            if (fo.delta16) run.vg8.add(a.dim > 8 ? masked_capacity(a.dim) : 8, t);
+        } else {
             run.any_generic = true;
+        }
     }
     pack.row_off[ntables] = ro;
     pack.occ_off[ntables] = oo;
@@ -790,15 +812,19 @@ inline int pack_adagrad_tables(int dtype, const et_adagrad_desc* descs, int ntab
 // The front of the pipeline, shared with et_weighted_adagrad: descriptor checks, the workspace,
 // then pack_adagrad_tables.  run.n == 0 on return means there is nothing to launch.
 inline int prepare_adagrad(int dtype, const et_adagrad_desc* descs, int ntables, bool rowwise,
-                           void* workspace, int64_t ws_bytes, void* stream, AdaRun& run) {
+                           void* workspace, int64_t ws_bytes, void* stream, AdaRun& run,
+                           const AdaFrontOpts& fo = AdaFrontOpts{}) {
     int rc = validate_adagrad(dtype, descs, ntables, rowwise, &run.n, &run.pdim, true);
     if (rc != ET_OK) return rc;
     if (run.n == 0) return ET_OK;
     run.w = carve_adagrad_ws(static_cast<char*>(workspace), run.n, run.pdim);
     if (!workspace || ws_bytes < run.w.bytes)
         return fail(ET_ERR_WORKSPACE, "workspace of %lld bytes needed", (long long)run.w.bytes);
-    return pack_adagrad_tables(dtype, descs, ntables, rowwise, stream, run, AdaFrontOpts{});
+    return pack_adagrad_tables(dtype, descs, ntables, rowwise, stream, run, fo);
 }
+
+// et_mixed_grad.hip: the chunk and combine passes of a call with a 16-bit gradient.
+inline int launch_adagrad_mixed(const AdaRun& r, uint32_t flags, float eta, float eps);
 
 }  // namespace et
 
@@ -819,12 +845,18 @@ extern "C" int et_sparse_adagrad(int dtype, const et_adagrad_desc* descs, int32_
                                  double eta, double eps, uint32_t flags, void* workspace,
                                  int64_t ws_bytes, void* stream) {
     et::clear_err();
-    int rc = et::check_adagrad_call(dtype, flags);
+    int rc = et::check_adagrad_call(dtype, flags, et::kDeltaFlags);
     if (rc != ET_OK) return rc;
     et::AdaRun run;
+    et::AdaFrontOpts fo;
+    if (flags & et::kDeltaFlags) {
+        fo.delta16 = true;
+        fo.vec_max_dim = ET_ADAM_VEC_MAX_DIM;
+    }
     rc = et::prepare_adagrad(dtype, descs, ntables, (flags & ET_FLAG_ADAGRAD_ROWWISE) != 0,
-                             workspace, ws_bytes, stream, run);
+                             workspace, ws_bytes, stream, run, fo);
     if (rc != ET_OK || run.n == 0) return rc;
+    if (fo.delta16) return et::launch_adagrad_mixed(run, flags, (float)eta, (float)eps);
     return et::dispatch_adagrad(dtype, flags, [&](auto e, auto row, auto nt) {
         using T = typename decltype(e)::type;
         using C = typename decltype(e)::acc;

@@ -454,7 +454,8 @@ __device__ __forceinline__ bool adam_partial_block(const C* __restrict__ partial
     return any != 0u;
 }
 
-template <typename T, typename C, bool ROW, bool NT>
+// G is the gradient's element type, as in k_adagrad_chunks_generic.
+template <typename T, typename C, bool ROW, bool NT, typename G = T>
 __global__ ET_ADAM_KERNEL __launch_bounds__(256) void k_adam_chunks_generic(
     UpdatePack pack, AdamPack ap, int ntables, const uint32_t* __restrict__ vals,
     const ChunkRec* __restrict__ recs, const uint32_t* __restrict__ counters,
@@ -470,13 +471,13 @@ __global__ ET_ADAM_KERNEL __launch_bounds__(256) void k_adam_chunks_generic(
         if ((pack.vec_mask >> t) & 1u) continue;  // the vector kernels' table
         const et_update_desc& d = pack.d[t];
         const int dim = d.dim;
-        const T* __restrict__ delta = reinterpret_cast<const T*>(d.delta);
+        const G* __restrict__ delta = reinterpret_cast<const G*>(d.delta);
         const uint64_t ldd = (uint64_t)d.ld_delta;
         const bool ragged = (ap.ragged >> t) & 1u;
         const uint32_t occ_off = pack.occ_off[t], pool = (uint32_t)d.pool;
         const uint32_t s0 = r.s0, s1 = r.s1;
         auto sum_block = [&](int f0, C(&acc)[kAdaK]) __attribute__((always_inline)) -> bool {
-            return adam_occ_block<T, C>(delta, ldd, dim, ragged, occ_off, pool, bag_ids, vals, s0,
+            return adam_occ_block<G, C>(delta, ldd, dim, ragged, occ_off, pool, bag_ids, vals, s0,
                                         s1, lane, f0, acc);
         };
         if (r.dst != kApply) {
@@ -601,17 +602,19 @@ inline int validate_adam_blocks(int dtype, const et_adam_desc* descs, int ntable
 
 constexpr uint32_t kAdamFlags = ET_FLAG_NONTEMPORAL | ET_FLAG_ADAM_ROWWISE;
 
-inline int check_adam_call(int dtype, uint32_t flags, double beta1, double beta2) {
+// `known`: flags beyond kAdamFlags this entry takes (kDeltaFlags for et_sparse_adam).
+inline int check_adam_call(int dtype, uint32_t flags, double beta1, double beta2,
+                           uint32_t known = 0) {
     if (dtype != ET_F32 && dtype != ET_F64 && dtype != ET_F16 && dtype != ET_BF16)
         return fail(ET_ERR_UNSUPPORTED, "sparse Adam: dtype %d", dtype);
     if (flags & kAdaSgdOnly)
         return fail(ET_ERR_UNSUPPORTED, "sparse Adam: flags 0x%x belong to the SGD",
                     flags & kAdaSgdOnly);
-    if (flags & ~kAdamFlags)
-        return fail(ET_ERR_ARG, "sparse Adam: unknown flags 0x%x", flags & ~kAdamFlags);
+    if (flags & ~(kAdamFlags | known))
+        return fail(ET_ERR_ARG, "sparse Adam: unknown flags 0x%x", flags & ~(kAdamFlags | known));
     if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0))
         return fail(ET_ERR_ARG, "sparse Adam: beta (%g, %g) outside [0, 1)", beta1, beta2);
-    return ET_OK;
+    return check_delta_flags("sparse Adam", dtype, flags & known);
 }
 
 template <typename F>
@@ -660,6 +663,10 @@ int launch_adam(const AdaRun& r, const UpdatePack& mpack, const AdamPack& ap, Ad
     return ET_OK;
 }
 
+// et_mixed_grad.hip: the advance, chunk and combine passes of a call with a 16-bit gradient.
+inline int launch_adam_mixed(const AdaRun& r, const UpdatePack& mpack, const AdamPack& ap,
+                             const AdamHyper<float>& h, uint32_t flags);
+
 }  // namespace et
 
 extern "C" int et_adam_workspace_size(const et_adam_desc* descs, int32_t ntables,
@@ -683,7 +690,7 @@ extern "C" int et_sparse_adam(int dtype, const et_adam_desc* descs, int32_t ntab
                               double beta1, double beta2, double eps, uint32_t flags,
                               void* workspace, int64_t ws_bytes, void* stream) {
     et::clear_err();
-    int rc = et::check_adam_call(dtype, flags, beta1, beta2);
+    int rc = et::check_adam_call(dtype, flags, beta1, beta2, et::kDeltaFlags);
     if (rc != ET_OK) return rc;
     rc = et::adam_table_count(descs, ntables);
     if (rc != ET_OK) return rc;
@@ -703,6 +710,7 @@ extern "C" int et_sparse_adam(int dtype, const et_adam_desc* descs, int32_t ntab
     et::AdaFrontOpts fo;
     fo.vec_max_dim = ET_ADAM_VEC_MAX_DIM;
     fo.kernel_clears = true;
+    fo.delta16 = (flags & et::kDeltaFlags) != 0;
     et::AdamPack ap{};
     for (int t = 0; t < ntables; ++t) {
         const et_adam_desc& d = descs[t];
@@ -721,6 +729,11 @@ extern "C" int et_sparse_adam(int dtype, const et_adam_desc* descs, int32_t ntab
     for (int t = 0; t < ntables; ++t) {
         mpack.d[t].idx = static_cast<const int64_t*>(descs[t].m);
         mpack.d[t].ld_idx = descs[t].ld_m;
+    }
+    if (fo.delta16) {
+        const et::AdamHyper<float> h{(float)eta,   (float)eps,           (float)beta1,
+                                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2)};
+        return et::launch_adam_mixed(run, mpack, ap, h, flags);
     }
     return et::dispatch_adagrad(dtype, flags, [&](auto e, auto row, auto nt) {
         using T = typename decltype(e)::type;

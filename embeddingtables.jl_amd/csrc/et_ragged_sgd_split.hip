@@ -506,6 +506,9 @@ extern "C" int et_ragged_sgd_split(int dtype, const et_weighted_update_desc* des
                  ET_FLAG_ADAGRAD_ROWWISE))
         return et::fail(ET_ERR_UNSUPPORTED, "split ragged SGD has no phased form, no hot-column "
                                             "pass and no row-wise form");
+    if (flags & et::kDeltaFlags)  // delta would be read as the table's type
+        return et::fail(ET_ERR_UNSUPPORTED, "split ragged SGD takes gradients of the table's "
+                                            "type only");
     et::SplitRun run;
     int rc = et::validate_split(descs, ntables, dtype == ET_F64 ? 8 : 4, true, &run.n, &run.pdim);
     if (rc != ET_OK || run.n == 0) return rc;

@@ -3771,6 +3771,9 @@ extern "C" int et_update_indexed(int dtype, void* table, int64_t ld_table,
 // Sparse Adam (et_sparse_adam): kernels and entry points.
 #include "et_adam.hip"
 
+// Float32 tables from Float16 / BFloat16 gradients (ET_FLAG_DELTA_*): chunk kernels, launches.
+#include "et_mixed_grad.hip"
+
 // Sparse Adam over weighted gradients (et_weighted_adam): pair pass, chunk kernels, entries.
 #include "et_weighted_adam.hip"
 

@@ -35,6 +35,8 @@ ET_FLAG_ADAGRAD_ROWWISE = 512
 ET_FLAG_ADAM_ROWWISE = 512  # the same bit: one row-wise flag per optimiser family
 ET_ADAM_VEC_MAX_DIM = 1024
 ET_FLAG_INTERACT_ITSELF = 1024
+ET_FLAG_DELTA_F16 = 2048   # et_sparse_adagrad / et_sparse_adam: Float32 table, Float16 gradient
+ET_FLAG_DELTA_BF16 = 4096  # ... BFloat16 gradient
 ET_INTERACT_MAX_VECTORS, ET_INTERACT_MAX_DIM = 32, 1024
 # include/embtab.h: the interaction grid is at most GRID_CAP workgroups of WAVES samples
 ET_INTERACT_WAVES, ET_INTERACT_GRID_CAP = 4, 2048

@@ -560,10 +560,23 @@ def _sgd_flags(fused: bool, nontemporal: bool, f64_alpha: bool = False,
     return flags
 
 
-def _update_desc(table: AbstractEmbeddingTable, grad: SparseEmbeddingUpdate) -> _lib.UpdateDesc:
+_DELTA_FLAGS = {torch.float16: _lib.ET_FLAG_DELTA_F16, torch.bfloat16: _lib.ET_FLAG_DELTA_BF16}
+
+
+def _delta_ok(table, delta, mixed: bool) -> bool:
+    """The gradient has the table's type, or (``mixed``: sparse AdaGrad and sparse Adam) it is
+    the Float16 / BFloat16 gradient of a Float32 table (ET_FLAG_DELTA_F16 / _BF16)."""
+    if table.dtype not in _UPDATE_DTYPES:
+        return False
+    return delta.dtype == table.dtype or (mixed and table.dtype == torch.float32
+                                          and delta.dtype in _DELTA_FLAGS)
+
+
+def _update_desc(table: AbstractEmbeddingTable, grad: SparseEmbeddingUpdate,
+                 mixed: bool = False) -> _lib.UpdateDesc:
     I = _check_idx(grad.indices)
     delta = grad.delta
-    if table.dtype not in _UPDATE_DTYPES or delta.dtype != table.dtype:
+    if not _delta_ok(table, delta, mixed):
         raise NotImplementedError(
             f"update of a {table.dtype} table with a {delta.dtype} gradient (supported: "
             "Float32 / Float64 / Float16 / BFloat16 tables with gradients of the same type)")
@@ -579,11 +592,11 @@ def _update_desc(table: AbstractEmbeddingTable, grad: SparseEmbeddingUpdate) -> 
                            I.data_ptr(), 1 if I.dim() == 1 else _ld(I), B, cpp)
 
 
-def _ragged_update_desc(table: AbstractEmbeddingTable,
-                        grad: SparseEmbeddingUpdate) -> _lib.RaggedUpdateDesc:
+def _ragged_update_desc(table: AbstractEmbeddingTable, grad: SparseEmbeddingUpdate,
+                        mixed: bool = False) -> _lib.RaggedUpdateDesc:
     R_ = _check_idx(grad.indices)
     delta = grad.delta
-    if table.dtype not in _UPDATE_DTYPES or delta.dtype != table.dtype:
+    if not _delta_ok(table, delta, mixed):
         raise NotImplementedError(
             f"update of a {table.dtype} table with a {delta.dtype} gradient (supported: "
             "Float32 / Float64 / Float16 / BFloat16 tables with gradients of the same type)")
@@ -783,7 +796,13 @@ def update_(*args, nontemporal: bool | None = None, exact: bool | None = None,
       ``ArgumentError`` unless the optimiser was built with ``Adam(..., weighted=True)``, which
       sends all its gradients through et_weighted_adam, grouped the same way.  The moments and the step state are allocated outside the C call, so
       they must exist before ``update_`` is captured into a HIP graph: call ``opt.state(A)``
-      and ``opt.step(A)`` first, or run one eager step."""
+      and ``opt.step(A)`` first, or run one eager step.
+    * With ``AdaGrad`` and ``Adam`` a Float32 table also takes a ``torch.float16`` or
+      ``torch.bfloat16`` gradient (ET_FLAG_DELTA_F16 / ET_FLAG_DELTA_BF16, one call per
+      (table type, gradient type)): the gradient is converted exactly as it is summed, so the
+      result equals the update with ``delta.float()`` without that copy.  ``Descent``, the
+      Indexer form, ``PhasedUpdate``, gradients that carry weights, optimisers built with
+      ``weighted=True`` and tables of any other type take gradients of the table's type only."""
     for a in args[:2]:  # the table(s): first or second argument in every form
         if isinstance(a, (AbstractEmbeddingTable, list, tuple)):
             refuse_quantized(a, "update_")
@@ -1054,15 +1073,26 @@ def _update_multi(opt: Descent, tables, grads, nontemporal: bool, exact: bool | 
                                        ws.numel(), stream))
 
 
+def _refuse_weighted_mixed(opt, tables, grads):
+    """The weighted entries take gradients of the table's type only."""
+    if opt.weighted:
+        for A, g in zip(tables, grads):
+            if g.delta.dtype != A.dtype:
+                raise ArgumentError(f"{type(opt).__name__}(weighted=True) with a {g.delta.dtype} "
+                                    f"gradient of a {A.dtype} table: et_weighted_"
+                                    f"{type(opt).__name__.lower()} takes gradients of the table's "
+                                    "type only")
+
+
 def _adagrad_desc(opt: AdaGrad, table, grad: SparseEmbeddingUpdate) -> _lib.AdaGradDesc:
     S = opt.state(table)
     ld_state = 1 if opt.rowwise else (int(S.stride(0)) if S.shape[0] > 1 else int(S.shape[1]))
     if isinstance(grad.indices, RaggedIndices):
-        r = _ragged_update_desc(table, grad)
+        r = _ragged_update_desc(table, grad, not opt.weighted)
         return _lib.AdaGradDesc(r.table, r.ld_table, r.nrows, r.dim, 1, r.delta, r.ld_delta,
                                 r.idx, 1, r.batch, r.cols_per_page, r.colptr, r.nnz,
                                 S.data_ptr(), ld_state)
-    u = _update_desc(table, grad)
+    u = _update_desc(table, grad, not opt.weighted)
     return _lib.AdaGradDesc(u.table, u.ld_table, u.nrows, u.dim, u.pool, u.delta, u.ld_delta,
                             u.idx, u.ld_idx, u.batch, u.cols_per_page, None, 0, S.data_ptr(),
                             ld_state)
@@ -1095,6 +1125,7 @@ def _update_adagrad(opt: AdaGrad, tables, grads, nontemporal: bool):
     if not opt.weighted and any(g.weights is not None for g in grads):
         raise ArgumentError("AdaGrad with a weighted gradient: build the optimiser with "
                             "weighted=True (et_weighted_adagrad)")
+    _refuse_weighted_mixed(opt, tables, grads)
     groups: dict = {}
     wgroups: dict = {}
     for A, g in zip(tables, grads):
@@ -1109,12 +1140,13 @@ def _update_adagrad(opt: AdaGrad, tables, grads, nontemporal: bool):
                 continue
         elif I.numel() == 0:
             continue
-        groups.setdefault(A.dtype, []).append(_adagrad_desc(opt, A, g))
+        groups.setdefault((A.dtype, g.delta.dtype), []).append(_adagrad_desc(opt, A, g))
     flags = (_lib.ET_FLAG_NONTEMPORAL if nontemporal else 0) | (
         _lib.ET_FLAG_ADAGRAD_ROWWISE if opt.rowwise else 0)
     L = _lib.load()
     ncall = 0
-    for dtype, descs in groups.items():
+    for (dtype, gtype), descs in groups.items():
+        gflag = _DELTA_FLAGS[gtype] if gtype != dtype else 0  # a 16-bit gradient: per call
         for c in range(0, len(descs), _lib.ET_MAX_TABLES_PER_LAUNCH):
             part = descs[c:c + _lib.ET_MAX_TABLES_PER_LAUNCH]
             arr = (_lib.AdaGradDesc * len(part))(*part)
@@ -1124,8 +1156,8 @@ def _update_adagrad(opt: AdaGrad, tables, grads, nontemporal: bool):
             dev = tables[0].device
             ws = _workspace(nb.value, dev, f"adagrad{ncall}")
             _lib.check(L.et_sparse_adagrad(_lib.TORCH_TO_ET[dtype], ctypes.addressof(arr),
-                                           len(part), opt.eta, opt.eps, flags, ws.data_ptr(),
-                                           ws.numel(), _lib.stream_handle(dev)))
+                                           len(part), opt.eta, opt.eps, flags | gflag,
+                                           ws.data_ptr(), ws.numel(), _lib.stream_handle(dev)))
             ncall += 1
     ncall = 0
     for dtype, descs in wgroups.items():
@@ -1149,10 +1181,10 @@ def _adam_desc(opt: Adam, table, grad: SparseEmbeddingUpdate) -> _lib.AdamDesc:
     tail = (m.data_ptr(), ld(m), v.data_ptr(), 1 if opt.rowwise else ld(v),
             opt.step(table).data_ptr())
     if isinstance(grad.indices, RaggedIndices):
-        r = _ragged_update_desc(table, grad)
+        r = _ragged_update_desc(table, grad, not opt.weighted)
         return _lib.AdamDesc(r.table, r.ld_table, r.nrows, r.dim, 1, r.delta, r.ld_delta, r.idx,
                              1, r.batch, r.cols_per_page, r.colptr, r.nnz, *tail)
-    u = _update_desc(table, grad)
+    u = _update_desc(table, grad, not opt.weighted)
     return _lib.AdamDesc(u.table, u.ld_table, u.nrows, u.dim, u.pool, u.delta, u.ld_delta, u.idx,
                          u.ld_idx, u.batch, u.cols_per_page, None, 0, *tail)
 
@@ -1188,6 +1220,7 @@ def _update_adam(opt: Adam, tables, grads, nontemporal: bool):
         raise ArgumentError("tables and grads differ in length")
     if not opt.weighted and any(g.weights is not None for g in grads):
         raise ArgumentError("Adam with a weighted gradient: et_sparse_adam takes none")
+    _refuse_weighted_mixed(opt, tables, grads)
     desc_of = _weighted_adam_desc if opt.weighted else _adam_desc
     groups: dict = {}
     for A, g in zip(tables, grads):
@@ -1197,7 +1230,7 @@ def _update_adam(opt: Adam, tables, grads, nontemporal: bool):
                 continue
         elif I.numel() == 0:
             continue
-        groups.setdefault(A.dtype, []).append(desc_of(opt, A, g))
+        groups.setdefault((A.dtype, g.delta.dtype), []).append(desc_of(opt, A, g))
     flags = (_lib.ET_FLAG_NONTEMPORAL if nontemporal else 0) | (
         _lib.ET_FLAG_ADAM_ROWWISE if opt.rowwise else 0)
     L = _lib.load()
@@ -1205,7 +1238,8 @@ def _update_adam(opt: Adam, tables, grads, nontemporal: bool):
                              L.et_weighted_adam, "weighted_adam") if opt.weighted else
                             (_lib.AdamDesc, L.et_adam_workspace_size, L.et_sparse_adam, "adam"))
     ncall = 0
-    for dtype, descs in groups.items():
+    for (dtype, gtype), descs in groups.items():
+        gflag = _DELTA_FLAGS[gtype] if gtype != dtype else 0  # a 16-bit gradient: per call
         for c in range(0, len(descs), _lib.ET_MAX_TABLES_PER_LAUNCH):
             part = descs[c:c + _lib.ET_MAX_TABLES_PER_LAUNCH]
             arr = (Desc * len(part))(*part)
@@ -1214,8 +1248,8 @@ def _update_adam(opt: Adam, tables, grads, nontemporal: bool):
             dev = tables[0].device
             ws = _workspace(nb.value, dev, f"{key}{ncall}")
             _lib.check(run(_lib.TORCH_TO_ET[dtype], ctypes.addressof(arr), len(part), opt.eta,
-                           opt.beta[0], opt.beta[1], opt.eps, flags, ws.data_ptr(), ws.numel(),
-                           _lib.stream_handle(dev)))
+                           opt.beta[0], opt.beta[1], opt.eps, flags | gflag, ws.data_ptr(),
+                           ws.numel(), _lib.stream_handle(dev)))
             ncall += 1
 
 

@@ -1160,6 +1160,10 @@ end
 #####
 
 const ET_FLAG_ADAM_ROWWISE = UInt32(512)
+# et_sparse_adagrad / et_sparse_adam, Float32 tables only: `delta` holds Float16 / BFloat16
+# elements (ld_delta counts them); the sum converts each value exactly to Float32.
+const ET_FLAG_DELTA_F16 = UInt32(2048)
+const ET_FLAG_DELTA_BF16 = UInt32(4096)
 
 struct AdamDesc
     table::Ptr{Cvoid}

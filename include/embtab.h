@@ -689,8 +689,9 @@ int et_ragged_sgd_split_workspace_size(const et_weighted_update_desc* descs, int
  * row stores), ET_FLAG_SGD_UNFUSED and ET_FLAG_SGD_F64_ALPHA select the apply step;
  * ET_FLAG_F16_FP32_ACC and ET_FLAG_EXACT_IF_FAST are accepted and change nothing;
  * ET_FLAG_EXACT_UPDATE is ET_ERR_ARG (the call is the opposite of exact);
- * ET_FLAG_SGD_INDEX_ONLY, ET_FLAG_SGD_APPLY_ONLY, ET_FLAG_SGD_HOT_PASS and
- * ET_FLAG_ADAGRAD_ROWWISE return ET_ERR_UNSUPPORTED.  ET_ERR_ARG before any device work: every
+ * ET_FLAG_SGD_INDEX_ONLY, ET_FLAG_SGD_APPLY_ONLY, ET_FLAG_SGD_HOT_PASS,
+ * ET_FLAG_ADAGRAD_ROWWISE, ET_FLAG_DELTA_F16 and ET_FLAG_DELTA_BF16 return
+ * ET_ERR_UNSUPPORTED.  ET_ERR_ARG before any device work: every
  * descriptor check of et_weighted_sgd except the NULL weights (NULL table, delta, idx or
  * colptr of a table with work, negative sizes, a leading dimension below dim, too many tables)
  * and weights not aligned to C.  Stream-ordered on the caller's stream only: no side streams,
@@ -1197,6 +1198,36 @@ int et_adam_workspace_size(const et_adam_desc* descs, int32_t ntables, int64_t* 
 int et_sparse_adam(int dtype, const et_adam_desc* descs, int32_t ntables, double eta,
                    double beta1, double beta2, double eps, uint32_t flags, void* workspace,
                    int64_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------
+ * Float32 tables updated from Float16 / BFloat16 gradients: two flag values of
+ * et_sparse_adagrad and et_sparse_adam (no new entry, struct or ABI version).  With one of
+ * them, `delta` is a matrix of 16-bit elements and `ld_delta` counts those elements
+ * (ld_delta >= dim as ever).  Valid with dtype == ET_F32 only (any other dtype:
+ * ET_ERR_UNSUPPORTED); both together: ET_ERR_ARG.  Every other rule of the two entries is
+ * unchanged: status codes before any device work, the workspace size (it does not depend on the
+ * flags: partial rows stay Float32), ET_FLAG_NONTEMPORAL, the row-wise flag, caller's stream
+ * only, capturable.  et_weighted_adagrad and et_weighted_adam reject the two bits as they
+ * reject any flag they do not know (ET_ERR_ARG); et_ragged_sgd_split returns
+ * ET_ERR_UNSUPPORTED; the SGD entries treat them as every bit they do not know.
+ *
+ * Arithmetic: the gradient sum g is the chunk rule of et_sparse_adagrad with
+ *   p_c = p_c + C(delta[:, bag])
+ * where C(.) is the exact conversion of a Float16 / BFloat16 value to Float32: every finite
+ * value, subnormals included, +-0 and +-Inf exactly; a NaN stays a NaN in its position.
+ * Everything after g is the optimiser's definition above, word for word.  So the table, the
+ * state or moments and the step state equal, bit for bit, the same call without the flag on
+ * delta converted to Float32 (row-wise: as far as the order of sum_f g_f^2, the kernel's
+ * choice, does not show).
+ *
+ * No byte of a gradient row beyond dim * 2 is read, nor any gradient column no occurrence names.
+ * Vector kernels (8 features per lane, one 16-byte load per gradient row and lane) serve tables
+ * with dim % 8 == 0, dim <= ET_ADAM_VEC_MAX_DIM, delta and ld_delta * 2 multiples of 16 bytes
+ * and the 16-byte rules of table, state and moments; every other table takes the generic
+ * kernels with the same results.
+ * ------------------------------------------------------------------------------- */
+#define ET_FLAG_DELTA_F16  2048u  /* et_sparse_adagrad / et_sparse_adam: delta is Float16  */
+#define ET_FLAG_DELTA_BF16 4096u  /* ... delta is BFloat16 */
 
 /* ---------------------------------------------------------------------------------
  * Sparse Adam over weighted gradients: the pullback of a weighted or mean-pooled lookup
